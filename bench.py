@@ -14,6 +14,13 @@ all-reduce overlap, fused multi-tensor SGD step.
 Timing contract: W untimed warmup steps; barrier + torch.cuda.synchronize();
 exactly K timed steps; barrier + synchronize; elapsed = MAX over ranks; one
 JSON line from rank 0.
+
+A plain run does only that.  ``--dump-outputs DIR`` additionally writes what
+the last timed step computed (loss, logits, a sample of the updated weights)
+as ``DIR/<name>.npy`` so two builds can be compared output for output; model
+weights and data are seeded, so the inputs repeat from run to run.  ``--full``
+is reserved for secondary measurements that need runs of their own; the
+benchmark currently has none, so it changes nothing.
 """
 
 from __future__ import annotations
@@ -51,7 +58,42 @@ def parse_args():
                         "the 313 ms step already hides launch overhead — so "
                         "off by default; capture verified correct on "
                         "hardware, world==1 only)")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="after the timed steps write the last step's outputs "
+                        "to DIR/<name>.npy (float32, rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (none today; a "
+                        "plain run times the headline figure only)")
     return p.parse_args()
+
+
+DUMP_CAP = 4 << 20  # elements per dumped array (16 MB of float32)
+
+
+def _sample(t, seed):
+    """Flat float32 numpy copy of ``t``; above DUMP_CAP elements a fixed,
+    seeded (sorted) sample of it so the dump stays small and comparable."""
+    t = t.detach().reshape(-1)
+    n = t.numel()
+    if n > DUMP_CAP:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(0, n, (DUMP_CAP,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, loss, logits, params):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"),
+            loss.detach().float().cpu().numpy())
+    if logits.numel() <= DUMP_CAP:
+        arr = logits.detach().float().cpu().numpy()
+    else:
+        arr = _sample(logits, 4321)
+    np.save(os.path.join(path, "logits.npy"), arr)
+    flat = torch.cat([p.detach().float().reshape(-1) for p in params])
+    np.save(os.path.join(path, "params.npy"), _sample(flat, 4322))
 
 
 def main():
@@ -88,6 +130,7 @@ def main():
     S = args.image_size
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
 
+    torch.manual_seed(1234)  # same initial weights every run (and rank)
     model = build_model(args.arch).to(device) \
         .to(memory_format=torch.channels_last)
     criterion = CrossEntropyLoss()
@@ -118,6 +161,8 @@ def main():
         .contiguous(memory_format=torch.channels_last)
     targets = torch.randint(0, 1000, (B,), generator=g).to(device)
 
+    last = {}  # the latest step's logits, for --dump-outputs
+
     def step():
         x = OF.normalize_u8(images_u8, dtype=dtype)
         if dtype == torch.bfloat16 and amp_handle is None:
@@ -125,6 +170,7 @@ def main():
                 out = model(x)
         else:
             out = model(x)
+        last["logits"] = out.detach()
         loss = criterion(out, targets)
         if hasattr(model, "reducer"):
             model.zero_grad()  # zero the bucket flats (grads are views)
@@ -222,6 +268,9 @@ def main():
                 "final_loss": round(float(loss.item()), 4),
             },
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loss, last["logits"],
+                         list(model.parameters()))
         print(json.dumps(result), flush=True)
 
     if world > 1:

@@ -76,6 +76,62 @@ def test_torchrun_bench_contract_cpu(tmp_path):
     assert d["scaling"] == "weak" and d["vs_baseline"] is not None
 
 
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy
+    files, and two runs with the same arguments start from the same seeded
+    weights and data, so their dumps agree."""
+    import json
+
+    import numpy as np
+    env = dict(os.environ, AMDTRAIN_BENCH_CPU="1",
+               AMDTRAIN_DISABLE_EXT="1", AMDTRAIN_ALLOW_EAGER="1",
+               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+               "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2",
+               "--arch", "resnet18", "--image-size", "32", "--dtype", "fp32",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, cwd=str(tmp_path), env=env,
+                           capture_output=True, text=True, timeout=420)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines()
+                        if l.startswith("{")][-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        arrs = {f: np.load(str(out / f))
+                for f in ("loss.npy", "logits.npy", "params.npy")}
+        assert all(a.dtype == np.float32 for a in arrs.values())
+        assert arrs["logits.npy"].shape == (2, 1000)
+        assert arrs["loss.npy"].size == 1
+        assert abs(float(arrs["loss.npy"]) - d["config"]["final_loss"]) < 1e-3
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(np.isfinite(a).all() for a in arrs.values())
+        dumps.append(arrs)
+    for f in dumps[0]:
+        np.testing.assert_allclose(dumps[0][f], dumps[1][f],
+                                   rtol=1e-4, atol=1e-5)
+
+
+def test_bench_full_flag_cpu(tmp_path):
+    """--full is accepted and still ends with the one JSON result line."""
+    import json
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+           "--steps", "1", "--warmup", "0", "--batch-per-gpu", "2",
+           "--arch", "resnet18", "--image-size", "32", "--dtype", "fp32",
+           "--full"]
+    env = dict(os.environ, AMDTRAIN_BENCH_CPU="1",
+               AMDTRAIN_DISABLE_EXT="1", AMDTRAIN_ALLOW_EAGER="1",
+               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True,
+                       text=True, timeout=420)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads(r.stdout.splitlines()[-1])
+    assert d["unit"] == "images/sec" and d["steps"] == 1
+
+
 def test_torchrun_bench_contract_styles_cpu(tmp_path):
     """The bench's --style apex/horovod variants must satisfy the same
     JSON contract as ddp (the styles share the timing harness; this
