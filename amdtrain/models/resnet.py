@@ -68,6 +68,21 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
         return OF.batch_norm(x, self, relu=True)
 
 
+def _shortcut_tail(out: torch.Tensor, bn: FusedBatchNorm2d,
+                   downsample: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """relu(bn(out) + downsample(x)).  A standard conv -> BN downsample in
+    training runs its BN inside the block tail's kernels
+    (``OF.bn_add_relu_downsample``: the normalized shortcut is never written
+    to memory); anything else keeps the module call."""
+    if (bn.training and isinstance(downsample, nn.Sequential)
+            and len(downsample) == 2
+            and isinstance(downsample[0], AmdConv2d)
+            and isinstance(downsample[1], FusedBatchNorm2d)):
+        return OF.bn_add_relu_downsample(out, bn, downsample[0](x),
+                                         downsample[1])
+    return OF.bn_add_relu(out, bn, downsample(x))
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -92,10 +107,9 @@ class BasicBlock(nn.Module):
         out = self.conv2(out)
         if cell is not None:
             cell.armed = True
-            tapped = ResidualGradTap.apply(x, cell)
-            identity = self.downsample(tapped)                 if self.downsample is not None else tapped
-        elif self.downsample is not None:
-            identity = self.downsample(x)
+            identity = ResidualGradTap.apply(x, cell)
+        if self.downsample is not None:
+            return _shortcut_tail(out, self.bn2, self.downsample, identity)
         return OF.bn_add_relu(out, self.bn2, identity)
 
 
@@ -136,10 +150,9 @@ class Bottleneck(nn.Module):
         out = self.conv3(out)
         if cell is not None:
             cell.armed = True
-            tapped = ResidualGradTap.apply(x, cell)
-            identity = self.downsample(tapped)                 if self.downsample is not None else tapped
-        elif self.downsample is not None:
-            identity = self.downsample(x)
+            identity = ResidualGradTap.apply(x, cell)
+        if self.downsample is not None:
+            return _shortcut_tail(out, self.bn3, self.downsample, identity)
         return OF.bn_add_relu(out, self.bn3, identity)
 
 
@@ -196,8 +209,8 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = self.bn1.forward_relu(self.conv1(x))
-        x = OF.max_pool_3x3_s2(x)
+        # BN+ReLU ride inside the pool's tap loop in training on GPU
+        x = OF.bn_relu_max_pool(self.conv1(x), self.bn1)
         x = self.layer1(x)
         x = self.layer2(x)
         x = self.layer3(x)

@@ -34,7 +34,21 @@ namespace {
 // GO2: go is the SUM of two operands (goB = the rerouted residual
 // shortcut gradient, see ResidualGradTap) — added in fp32 here so the
 // eager CUDAFunctor_add pass disappears; the sum is baked into ghat_out.
-template <typename T, int VEC, bool BWD, int MASK, bool WG, bool GO2>
+// DUAL (downsample block tail): the shortcut is a second BN over x_d whose
+// grad_out IS ghat, so its two sums ride in the same row loop.  They are
+// taken over the ROUNDED ghat (what the separate pass read back from
+// memory), hence four sums per channel: with GO2 the fp32 go+go2 and its
+// rounding differ.  Same grid / row partition / fold order as two passes.
+template <typename T>
+struct BNDualSide {
+  const T* x = nullptr;
+  const float* mean = nullptr;
+  const float* invstd = nullptr;
+  float* out = nullptr;
+};
+
+template <typename T, int VEC, bool BWD, int MASK, bool WG, bool GO2,
+          bool DUAL = false>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
                  const T* __restrict__ goB, const T* __restrict__ y,
@@ -42,7 +56,9 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
                  const float* __restrict__ invstd,
                  const float* __restrict__ scale,
                  const float* __restrict__ shift, T* __restrict__ ghat_out,
-                 float* __restrict__ out, long R, int C) {
+                 float* __restrict__ out, long R, int C,
+                 BNDualSide<T> ds = {}) {
+  static_assert(!DUAL || (BWD && WG), "DUAL rides the ghat-writing bwd pass");
   const int t = threadIdx.x;
   const int gpr = C / VEC;  // channel-groups per row
   // rows are split across blocks
@@ -60,6 +76,7 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
 #pragma unroll
     for (int k = 0; k < VEC; ++k) sa[k] = sb[k] = 0.f;
     float mk[VEC], ik[VEC], sck[VEC], shk[VEC];
+    float sda[VEC], sdb[VEC], mdk[VEC], idk[VEC];  // DUAL: downsample BN
     if (BWD) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
@@ -69,15 +86,21 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
           sck[k] = scale[c0 + k];
           shk[k] = shift[c0 + k];
         }
+        if (DUAL) {
+          sda[k] = sdb[k] = 0.f;
+          mdk[k] = ds.mean[c0 + k];
+          idk[k] = ds.invstd[c0 + k];
+        }
       }
     }
     for (long r = r0 + phase; r < r1; r += rstep) {
       const long base = r * C + c0;
       Pack<T, VEC> xv = *(const Pack<T, VEC>*)(x + base);
-      Pack<T, VEC> gv, gv2, yv, gh;
+      Pack<T, VEC> gv, gv2, yv, gh, dv;
       unsigned int mbits = 0;
       if (BWD) {
         gv = *(const Pack<T, VEC>*)(go + base);
+        if (DUAL) dv = *(const Pack<T, VEC>*)(ds.x + base);
         if (GO2) gv2 = *(const Pack<T, VEC>*)(goB + base);
         if (MASK == 1) yv = *(const Pack<T, VEC>*)(y + base);
         if (MASK == 3)
@@ -95,6 +118,11 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
           sa[k] += ge;
           sb[k] += ge * (xe - mk[k]) * ik[k];
           if (WG) gh.v[k] = from_f32<T>(ge);
+          if (DUAL) {
+            const float gr = to_f32(gh.v[k]);
+            sda[k] += gr;
+            sdb[k] += gr * (to_f32(dv.v[k]) - mdk[k]) * idk[k];
+          }
         } else {
           sa[k] += xe;
           sb[k] += xe * xe;
@@ -102,26 +130,27 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
       }
       if (BWD && WG) *(Pack<T, VEC>*)(ghat_out + base) = gh;
     }
-    // LDS reduce across phases, then one global atomicAdd per channel
+    // LDS reduce across phases into phase 0, one sum array at a time
     __shared__ float lds[AMD_TPB * VEC];
+    auto fold = [&](float(&s)[VEC]) {
 #pragma unroll
-    for (int k = 0; k < VEC; ++k) lds[t * VEC + k] = sa[k];
-    __syncthreads();
-    if (phase == 0) {
-      for (int ph = 1; ph < rstep; ++ph)
+      for (int k = 0; k < VEC; ++k) lds[t * VEC + k] = s[k];
+      __syncthreads();
+      if (phase == 0) {
+        for (int ph = 1; ph < rstep; ++ph)
 #pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          sa[k] += lds[(ph * gpr + gc) * VEC + k];
+          for (int k = 0; k < VEC; ++k)
+            s[k] += lds[(ph * gpr + gc) * VEC + k];
+      }
+      __syncthreads();
+    };
+    fold(sa);
+    fold(sb);
+    if (DUAL) {
+      fold(sda);
+      fold(sdb);
     }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) lds[t * VEC + k] = sb[k];
-    __syncthreads();
     if (phase == 0) {
-      for (int ph = 1; ph < rstep; ++ph)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k)
-          sb[k] += lds[(ph * gpr + gc) * VEC + k];
       // per-block partials (no global atomics: 1024-way same-line atomic
       // contention was ~24 ms/step — two-stage instead)
       float* part = out + (long)blockIdx.x * 2 * C;
@@ -130,9 +159,18 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
         part[c0 + k] = sa[k];
         part[C + c0 + k] = sb[k];
       }
+      if (DUAL) {
+        float* partd = ds.out + (long)blockIdx.x * 2 * C;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+          partd[c0 + k] = sda[k];
+          partd[C + c0 + k] = sdb[k];
+        }
+      }
     }
   } else {
     // wide-C: each thread owns up to 2 channel-groups, no cross-thread reduce
+    // (DUAL is register-path only; the host entry rejects wide-C)
     const int cpt = gpr / AMD_TPB;  // host guarantees <= 2 and divisible
     float sa[2][VEC], sb[2][VEC];
     float mk[2][VEC], ik[2][VEC], sck[2][VEC], shk[2][VEC];
@@ -156,10 +194,13 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
         const long base = r * C + c0;
         Pack<T, VEC> xv = *(const Pack<T, VEC>*)(x + base);
         Pack<T, VEC> gv, gv2, yv, gh;
+        unsigned int mbits = 0;
         if (BWD) {
           gv = *(const Pack<T, VEC>*)(go + base);
           if (GO2) gv2 = *(const Pack<T, VEC>*)(goB + base);
           if (MASK == 1) yv = *(const Pack<T, VEC>*)(y + base);
+          if (MASK == 3)
+            mbits = ((const unsigned char*)y)[base / VEC];
         }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
@@ -169,6 +210,7 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
             if (GO2) ge += to_f32(gv2.v[k]);
             if (MASK == 1 && to_f32(yv.v[k]) <= 0.f) ge = 0.f;
             if (MASK == 2 && sck[j][k] * xe + shk[j][k] <= 0.f) ge = 0.f;
+            if (MASK == 3 && !(mbits & (1u << k))) ge = 0.f;
             sa[j][k] += ge;
             sb[j][k] += ge * (xe - mk[j][k]) * ik[j][k];
             if (WG) gh.v[k] = from_f32<T>(ge);
@@ -274,20 +316,46 @@ __global__ void bn_finalize_eval_kernel(
 // 2-way unrolled (two independent 16 B streams in flight per thread) with a
 // pow2 fast path for the channel-group decompose (all ResNet C are pow2;
 // the 64-bit % was ~25 VALU cycles per 16 B).
-template <typename T, int VEC, bool RELU, bool HAS_ADD, bool POW2>
+// DUAL (downsample block tail): z is the RAW downsample-conv output and the
+// addend is its own BN, T(scale_d*z + shift_d) — rounded through the
+// activation dtype exactly as the materialized intermediate was, so the
+// separate downsample apply (1r+1w) disappears without changing a bit.
+// Its four coefficient sets stay in registers (measured +0.7% end to end
+// over [4][C] in LDS).
+template <typename T, int VEC, bool RELU, bool HAS_ADD, bool POW2,
+          bool DUAL = false>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
                 T* __restrict__ y, unsigned char* __restrict__ mask,
                 const float* __restrict__ scale,
-                const float* __restrict__ shift, long total_vec, int C) {
-  extern __shared__ float sm[];  // [2][C]
+                const float* __restrict__ shift, long total_vec, int C,
+                const float* __restrict__ scale_d = nullptr,
+                const float* __restrict__ shift_d = nullptr) {
+  static_assert(!DUAL || (HAS_ADD && POW2), "DUAL normalizes the addend");
+  extern __shared__ float sm[];  // [2][C] (unused by DUAL)
   const int gpr = C / VEC;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    sm[c] = scale[c];
-    sm[C + c] = shift[c];
-  }
-  __syncthreads();
   const long stride = (long)gridDim.x * blockDim.x;
+  // DUAL: the host admits only pow2 C/VEC <= blockDim, so the grid stride
+  // is a multiple of C/VEC and a thread keeps ONE channel group for the
+  // whole loop — its four coefficient sets live in registers, not LDS.
+  float rs[VEC], rb[VEC], rsd[VEC], rbd[VEC];
+  if (DUAL) {
+    const int cf =
+        (int)(((long)blockIdx.x * blockDim.x + threadIdx.x) & (gpr - 1)) * VEC;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      rs[k] = scale[cf + k];
+      rb[k] = shift[cf + k];
+      rsd[k] = scale_d[cf + k];
+      rbd[k] = shift_d[cf + k];
+    }
+  } else {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      sm[c] = scale[c];
+      sm[C + c] = shift[c];
+    }
+    __syncthreads();
+  }
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec;
        i += 2 * stride) {
     const bool has2 = i + stride < total_vec;
@@ -305,15 +373,25 @@ bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
     unsigned int mb = 0, mb2 = 0;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      float v = sm[c0 + k] * to_f32(xv.v[k]) + sm[C + c0 + k];
-      if (HAS_ADD) v += to_f32(zv.v[k]);
+      float v = DUAL ? rs[k] * to_f32(xv.v[k]) + rb[k]
+                     : sm[c0 + k] * to_f32(xv.v[k]) + sm[C + c0 + k];
+      if (HAS_ADD) {
+        float ze = to_f32(zv.v[k]);
+        if (DUAL) ze = to_f32(from_f32<T>(rsd[k] * ze + rbd[k]));
+        v += ze;
+      }
       if (RELU) {
         if (mask != nullptr && v > 0.f) mb |= 1u << k;
         v = fmaxf(v, 0.f);
       }
       yv.v[k] = from_f32<T>(v);
-      float v2 = sm[c02 + k] * to_f32(xv2.v[k]) + sm[C + c02 + k];
-      if (HAS_ADD) v2 += to_f32(zv2.v[k]);
+      float v2 = DUAL ? rs[k] * to_f32(xv2.v[k]) + rb[k]
+                      : sm[c02 + k] * to_f32(xv2.v[k]) + sm[C + c02 + k];
+      if (HAS_ADD) {
+        float ze2 = to_f32(zv2.v[k]);
+        if (DUAL) ze2 = to_f32(from_f32<T>(rsd[k] * ze2 + rbd[k]));
+        v2 += ze2;
+      }
       if (RELU) {
         if (mask != nullptr && v2 > 0.f) mb2 |= 1u << k;
         v2 = fmaxf(v2, 0.f);
@@ -367,14 +445,81 @@ __global__ void bn_bwd_finalize_kernel(
 // already masked (the reduce pass wrote ghat, or no relu) — no y read at
 // all; MASK 2: relu mask recomputed from the forward's scale/shift
 // (y = relu(scale*x+shift) so y>0 <=> scale*x+shift>0) — also no y read.
-template <typename T, int VEC, int MASK, bool WRITE_GHAT, bool POW2>
+// DUAL (downsample block tail): the shortcut BN shares ghat, so one pass
+// reads x, x_d, ghat and writes gx and gx_d, each with its own A/B/D —
+// the downsample BN's separate apply no longer re-reads ghat.
+template <typename T>
+struct BNDualBwdSide {
+  const T* x = nullptr;
+  T* gx = nullptr;
+  const float* A = nullptr;
+  const float* Bc = nullptr;
+  const float* Dc = nullptr;
+};
+
+template <typename T, int VEC, int MASK, bool WRITE_GHAT, bool POW2,
+          bool DUAL = false>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
                     T* __restrict__ gx,
                     T* __restrict__ ghat_out, const float* __restrict__ A,
                     const float* __restrict__ Bc, const float* __restrict__ Dc,
                     const float* __restrict__ scale,
-                    const float* __restrict__ shift, long total_vec, int C) {
+                    const float* __restrict__ shift, long total_vec, int C,
+                    BNDualBwdSide<T> ds = {}) {
+  static_assert(!DUAL || (MASK == 0 && POW2 && !WRITE_GHAT),
+                "DUAL consumes the materialized ghat");
+  const int gpr = C / VEC;
+  const long stride = (long)gridDim.x * blockDim.x;
+  if (DUAL) {
+    // The host admits only pow2 C/VEC <= blockDim here, so the grid stride
+    // is a multiple of C/VEC and a thread keeps ONE channel group for the
+    // whole loop: all six coefficient sets live in registers (six [C]
+    // arrays in LDS would be 48 KB/block at C=2048 — 3 blocks/CU).
+    const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c0 = (int)(i0 & (gpr - 1)) * VEC;
+    float a3[VEC], b3[VEC], d3[VEC], ad[VEC], bd[VEC], dd[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      a3[k] = A[c0 + k];
+      b3[k] = Bc[c0 + k];
+      d3[k] = Dc[c0 + k];
+      ad[k] = ds.A[c0 + k];
+      bd[k] = ds.Bc[c0 + k];
+      dd[k] = ds.Dc[c0 + k];
+    }
+    for (long i = i0; i < total_vec; i += 2 * stride) {
+      const bool has2 = i + stride < total_vec;
+      const long i2 = has2 ? i + stride : i;  // clamp: loads stay in bounds
+      Pack<T, VEC> xv = *(const Pack<T, VEC>*)(x + i * VEC);
+      Pack<T, VEC> dv = *(const Pack<T, VEC>*)(ds.x + i * VEC);
+      Pack<T, VEC> gv = *(const Pack<T, VEC>*)(go + i * VEC);
+      Pack<T, VEC> xv2 = *(const Pack<T, VEC>*)(x + i2 * VEC);
+      Pack<T, VEC> dv2 = *(const Pack<T, VEC>*)(ds.x + i2 * VEC);
+      Pack<T, VEC> gv2 = *(const Pack<T, VEC>*)(go + i2 * VEC);
+      Pack<T, VEC> out, dout, out2, dout2;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        float ge = to_f32(gv.v[k]);
+        float v = a3[k] * ge + b3[k] * to_f32(xv.v[k]) + d3[k];
+        out.v[k] = from_f32<T>(v);
+        float w = ad[k] * ge + bd[k] * to_f32(dv.v[k]) + dd[k];
+        dout.v[k] = from_f32<T>(w);
+        float ge2 = to_f32(gv2.v[k]);
+        float v2 = a3[k] * ge2 + b3[k] * to_f32(xv2.v[k]) + d3[k];
+        out2.v[k] = from_f32<T>(v2);
+        float w2 = ad[k] * ge2 + bd[k] * to_f32(dv2.v[k]) + dd[k];
+        dout2.v[k] = from_f32<T>(w2);
+      }
+      *(Pack<T, VEC>*)(gx + i * VEC) = out;
+      *(Pack<T, VEC>*)(ds.gx + i * VEC) = dout;
+      if (has2) {
+        *(Pack<T, VEC>*)(gx + i2 * VEC) = out2;
+        *(Pack<T, VEC>*)(ds.gx + i2 * VEC) = dout2;
+      }
+    }
+    return;
+  }
   extern __shared__ float sm[];  // [3][C] (+[2][C] for MASK 2)
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     sm[c] = A[c];
@@ -386,8 +531,6 @@ bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
     }
   }
   __syncthreads();
-  const int gpr = C / VEC;
-  const long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec;
        i += 2 * stride) {
     const bool has2 = i + stride < total_vec;
@@ -459,7 +602,121 @@ static int bn_reduce_grid(long R, int C) {
   return (int)std::min<long>((R + rows_per_block - 1) / rows_per_block, 1536);
 }
 
+// collapse [nparts][2C] per-block partials to the few slots the finalize
+// kernels loop over
+static at::Tensor bn_collapse(const at::Tensor& parts, long C,
+                              hipStream_t stream) {
+  const int nparts = (int)parts.size(0);
+  const int slots = bn_collapse_slots(nparts);
+  auto sums2 = at::empty({slots, 2 * C}, parts.options());
+  int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
+  bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
+      parts.data_ptr<float>(), sums2.data_ptr<float>(), nparts, (int)(2 * C),
+      slots);
+  CHECK_CUDA_OK();
+  return sums2;
+}
+
+struct BNTrainStats {
+  at::Tensor mean, invstd, scale, shift;
+};
+
+// training-mode statistics stage shared by every forward entry:
+// [reduce over x unless the producing conv's epilogue already left
+// partials] -> collapse -> finalize (+ running-stat update)
+static BNTrainStats bn_train_stats(const at::Tensor& x,
+                                   const std::optional<at::Tensor>& parts,
+                                   const at::Tensor& weight,
+                                   const at::Tensor& bias,
+                                   at::Tensor& running_mean,
+                                   at::Tensor& running_var, double momentum,
+                                   double eps) {
+  const long C = x.size(1);
+  const long R = x.numel() / C;
+  auto opts = x.options().dtype(at::kFloat);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  at::Tensor sums;
+  if (parts) {
+    TORCH_CHECK(parts->size(1) == 2 * C, "parts must be [nparts][2C]");
+    sums = *parts;
+  } else {
+    const int rgrid = bn_reduce_grid(R, C);
+    sums = at::empty({rgrid, 2 * C}, opts);
+    dispatch_vec(x, [&](auto* tp, auto vec) {
+      using devT = std::remove_pointer_t<decltype(tp)>;
+      constexpr int VEC = decltype(vec)::value;
+      bn_reduce_kernel<devT, VEC, false, 0, false, false>
+          <<<rgrid, AMD_TPB, 0, stream>>>((const devT*)x.const_data_ptr(),
+                                          nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, nullptr, nullptr,
+                                          sums.data_ptr<float>(), R, (int)C);
+      CHECK_CUDA_OK();
+    });
+  }
+  auto sums2 = bn_collapse(sums, C, stream);
+  BNTrainStats s{at::empty({C}, opts), at::empty({C}, opts),
+                 at::empty({C}, opts), at::empty({C}, opts)};
+  int fgrid = (int)((C + 63) / 64);
+  bn_finalize_train_kernel<<<fgrid, AMD_TPB, 0, stream>>>(
+      sums2.data_ptr<float>(), (int)sums2.size(0), weight.data_ptr<float>(),
+      bias.data_ptr<float>(), running_mean.data_ptr<float>(),
+      running_var.data_ptr<float>(), s.mean.data_ptr<float>(),
+      s.invstd.data_ptr<float>(), s.scale.data_ptr<float>(),
+      s.shift.data_ptr<float>(), R, (int)C, (float)momentum, (float)eps);
+  CHECK_CUDA_OK();
+  return s;
+}
+
+struct BNBwdCoeffs {
+  at::Tensor gw, gb, A, Bc, Dc;
+};
+
+// backward collapse -> finalize: grad_w/grad_b + the apply's A,B,D
+static BNBwdCoeffs bn_bwd_coeffs(const at::Tensor& sums,
+                                 const at::Tensor& weight,
+                                 const at::Tensor& mean,
+                                 const at::Tensor& invstd, long R, long C) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  auto opts = sums.options();
+  auto sums2 = bn_collapse(sums, C, stream);
+  BNBwdCoeffs k{at::empty({C}, opts), at::empty({C}, opts),
+                at::empty({C}, opts), at::empty({C}, opts),
+                at::empty({C}, opts)};
+  int fgrid = (int)((C + 63) / 64);
+  bn_bwd_finalize_kernel<<<fgrid, AMD_TPB, 0, stream>>>(
+      sums2.data_ptr<float>(), (int)sums2.size(0), weight.data_ptr<float>(),
+      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+      k.gw.data_ptr<float>(), k.gb.data_ptr<float>(), k.A.data_ptr<float>(),
+      k.Bc.data_ptr<float>(), k.Dc.data_ptr<float>(), R, (int)C);
+  CHECK_CUDA_OK();
+  return k;
+}
+
+// the dual-BN tail is register-path only: same C on both sides and
+// C/VEC within one block (wide-C would need its own masked branch)
+static void check_dual(const at::Tensor& x3, const at::Tensor& x_d) {
+  check_nhwc(x3);
+  check_nhwc(x_d);
+  TORCH_CHECK(x3.sizes() == x_d.sizes() &&
+                  x3.scalar_type() == x_d.scalar_type(),
+              "dual BN tail: x3 and x_d must match in shape and dtype");
+  TORCH_CHECK(x3.size(1) * (long)x3.element_size() / 16 <= AMD_TPB,
+              "dual BN tail: C too wide for the register path: ", x3.size(1));
+}
+
 }  // namespace
+
+// statistics stage alone (mean, invstd, scale, shift + running update) for
+// consumers that apply scale/shift inside their own kernel (stem max pool)
+std::vector<at::Tensor> batch_norm_train_stats(
+    at::Tensor x, std::optional<at::Tensor> parts, at::Tensor weight,
+    at::Tensor bias, at::Tensor running_mean, at::Tensor running_var,
+    double momentum, double eps) {
+  check_nhwc(x);
+  auto s = bn_train_stats(x, parts, weight, bias, running_mean, running_var,
+                          momentum, eps);
+  return {s.mean, s.invstd, s.scale, s.shift};
+}
 
 std::vector<at::Tensor> batch_norm_fwd_train(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
@@ -468,13 +725,6 @@ std::vector<at::Tensor> batch_norm_fwd_train(
   check_nhwc(x);
   const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const long R = N * H * W;
-  auto opts = x.options().dtype(at::kFloat);
-  const int rgrid = bn_reduce_grid(R, C);
-  auto sums = at::empty({rgrid, 2 * C}, opts);
-  auto mean = at::empty({C}, opts);
-  auto invstd = at::empty({C}, opts);
-  auto scale = at::empty({C}, opts);
-  auto shift = at::empty({C}, opts);
   auto y = at::empty_like(x);
   // block-tail BNs (relu+addend) also emit a 1-bit relu mask (1/16 the
   // bytes of y) so the bwd reduce skips the y read entirely
@@ -482,33 +732,14 @@ std::vector<at::Tensor> batch_norm_fwd_train(
   if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
   auto stream = at::cuda::getCurrentCUDAStream();
+  auto st = bn_train_stats(x, std::nullopt, weight, bias, running_mean,
+                           running_var, momentum, eps);
+  auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
+       &shift = st.shift;
 
   dispatch_vec(x, [&](auto* tp, auto vec) {
     using devT = std::remove_pointer_t<decltype(tp)>;
     constexpr int VEC = decltype(vec)::value;
-    bn_reduce_kernel<devT, VEC, false, 0, false, false>
-        <<<rgrid, AMD_TPB, 0, stream>>>((const devT*)x.const_data_ptr(),
-                                        nullptr, nullptr, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr,
-                                        sums.data_ptr<float>(), R, (int)C);
-    CHECK_CUDA_OK();
-    const int slots = bn_collapse_slots(rgrid);
-    auto sums2 = at::empty({slots, 2 * C}, opts);
-    {
-      int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
-      bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
-          sums.data_ptr<float>(), sums2.data_ptr<float>(), rgrid,
-          (int)(2 * C), slots);
-      CHECK_CUDA_OK();
-    }
-    int fgrid = (int)((C + 63) / 64);
-    bn_finalize_train_kernel<<<fgrid, AMD_TPB, 0, stream>>>(
-        sums2.data_ptr<float>(), slots, weight.data_ptr<float>(),
-        bias.data_ptr<float>(), running_mean.data_ptr<float>(),
-        running_var.data_ptr<float>(), mean.data_ptr<float>(),
-        invstd.data_ptr<float>(), scale.data_ptr<float>(),
-        shift.data_ptr<float>(), R, (int)C, (float)momentum, (float)eps);
-    CHECK_CUDA_OK();
     long total_vec = R * C / VEC;
     int agrid = amd_grid(total_vec);
     size_t smem = 2 * C * sizeof(float);
@@ -541,36 +772,15 @@ std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
   check_nhwc(x);
   const long C = x.size(1);
   const long R = x.numel() / C;
-  TORCH_CHECK(parts.size(1) == 2 * C, "parts must be [nparts][2C]");
-  const int nparts = (int)parts.size(0);
-  auto opts = x.options().dtype(at::kFloat);
-  auto mean = at::empty({C}, opts);
-  auto invstd = at::empty({C}, opts);
-  auto scale = at::empty({C}, opts);
-  auto shift = at::empty({C}, opts);
   auto y = at::empty_like(x);
   at::Tensor mask;
   if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
   auto stream = at::cuda::getCurrentCUDAStream();
-
-  const int slots = bn_collapse_slots(nparts);
-  auto sums2 = at::empty({slots, 2 * C}, opts);
-  {
-    int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
-    bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
-        parts.data_ptr<float>(), sums2.data_ptr<float>(), nparts,
-        (int)(2 * C), slots);
-    CHECK_CUDA_OK();
-  }
-  int fgrid = (int)((C + 63) / 64);
-  bn_finalize_train_kernel<<<fgrid, AMD_TPB, 0, stream>>>(
-      sums2.data_ptr<float>(), slots, weight.data_ptr<float>(),
-      bias.data_ptr<float>(), running_mean.data_ptr<float>(),
-      running_var.data_ptr<float>(), mean.data_ptr<float>(),
-      invstd.data_ptr<float>(), scale.data_ptr<float>(),
-      shift.data_ptr<float>(), R, (int)C, (float)momentum, (float)eps);
-  CHECK_CUDA_OK();
+  auto st = bn_train_stats(x, parts, weight, bias, running_mean, running_var,
+                           momentum, eps);
+  auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
+       &shift = st.shift;
   dispatch_vec(x, [&](auto* tp, auto vec) {
     using devT = std::remove_pointer_t<decltype(tp)>;
     constexpr int VEC = decltype(vec)::value;
@@ -595,6 +805,106 @@ std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
   });
   if (!mask.defined()) mask = at::empty({0}, x.options().dtype(at::kByte));
   return {y, mean, invstd, scale, shift, mask};
+}
+
+// Downsample block tail, forward: y = relu(bn3(x3) + T(bn_d(x_d))) with the
+// downsample BN's output never materialized.  Each side takes its
+// statistics from conv-epilogue partials when it has them, else from the
+// reduce pass (the strided downsample convs emit none).
+// Returns {y, mean3, invstd3, mean_d, invstd_d, mask}.
+std::vector<at::Tensor> batch_norm_dual_fwd_train(
+    at::Tensor x3, at::Tensor x_d, std::optional<at::Tensor> parts3,
+    std::optional<at::Tensor> parts_d, at::Tensor weight3, at::Tensor bias3,
+    at::Tensor running_mean3, at::Tensor running_var3, double momentum3,
+    double eps3, at::Tensor weight_d, at::Tensor bias_d,
+    at::Tensor running_mean_d, at::Tensor running_var_d, double momentum_d,
+    double eps_d) {
+  check_dual(x3, x_d);
+  const long C = x3.size(1);
+  const long R = x3.numel() / C;
+  auto sd = bn_train_stats(x_d, parts_d, weight_d, bias_d, running_mean_d,
+                           running_var_d, momentum_d, eps_d);
+  auto s3 = bn_train_stats(x3, parts3, weight3, bias3, running_mean3,
+                           running_var3, momentum3, eps3);
+  auto y = at::empty_like(x3);
+  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
+  auto mask = at::empty({R * C / 4}, x3.options().dtype(at::kByte));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dispatch_vec(x3, [&](auto* tp, auto vec) {
+    using devT = std::remove_pointer_t<decltype(tp)>;
+    constexpr int VEC = decltype(vec)::value;
+    long total_vec = R * C / VEC;
+    int agrid = amd_grid(total_vec);
+    bn_apply_kernel<devT, VEC, true, true, true, true>
+        <<<agrid, AMD_TPB, 0, stream>>>(
+            (const devT*)x3.const_data_ptr(),
+            (const devT*)x_d.const_data_ptr(), (devT*)y.data_ptr(),
+            mask.data_ptr<unsigned char>(), s3.scale.data_ptr<float>(),
+            s3.shift.data_ptr<float>(), total_vec, (int)C,
+            sd.scale.data_ptr<float>(), sd.shift.data_ptr<float>());
+    CHECK_CUDA_OK();
+  });
+  return {y, s3.mean, s3.invstd, sd.mean, sd.invstd, mask};
+}
+
+// Downsample block tail, backward: one reduce (x3, x_d, go[, go2], mask ->
+// ghat + both BNs' sums) and one apply (x3, x_d, ghat -> gx3, gx_d).
+// Returns {gx3, gw3, gb3, gx_d, gw_d, gb_d}.
+std::vector<at::Tensor> batch_norm_dual_bwd(
+    at::Tensor x3, at::Tensor x_d, at::Tensor grad_out,
+    std::optional<at::Tensor> grad_out2, at::Tensor relu_mask,
+    at::Tensor weight3, at::Tensor mean3, at::Tensor invstd3,
+    at::Tensor weight_d, at::Tensor mean_d, at::Tensor invstd_d) {
+  check_dual(x3, x_d);
+  check_nhwc(grad_out);
+  const long C = x3.size(1);
+  const long R = x3.numel() / C;
+  TORCH_CHECK(relu_mask.numel() == R * C / 4, "relu_mask size mismatch");
+  auto opts = x3.options().dtype(at::kFloat);
+  const int rgrid = bn_reduce_grid(R, C);
+  auto sums3 = at::empty({rgrid, 2 * C}, opts);
+  auto sums_d = at::empty({rgrid, 2 * C}, opts);
+  auto ghat = at::empty_like(grad_out);
+  auto gx3 = at::empty_like(x3);
+  auto gx_d = at::empty_like(x_d);
+  BNBwdCoeffs k3, kd;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dispatch_vec(x3, [&](auto* tp, auto vec) {
+    using devT = std::remove_pointer_t<decltype(tp)>;
+    constexpr int VEC = decltype(vec)::value;
+    const devT* go2p = grad_out2
+        ? (const devT*)grad_out2->const_data_ptr() : nullptr;
+    BNDualSide<devT> rs{(const devT*)x_d.const_data_ptr(),
+                        mean_d.data_ptr<float>(), invstd_d.data_ptr<float>(),
+                        sums_d.data_ptr<float>()};
+#define REDUCE_DUAL(GO2_)                                                   \
+  bn_reduce_kernel<devT, VEC, true, 3, true, GO2_, true>                    \
+      <<<rgrid, AMD_TPB, 0, stream>>>(                                      \
+          (const devT*)x3.const_data_ptr(),                                 \
+          (const devT*)grad_out.const_data_ptr(), go2p,                     \
+          (const devT*)relu_mask.const_data_ptr(), mean3.data_ptr<float>(), \
+          invstd3.data_ptr<float>(), nullptr, nullptr,                      \
+          (devT*)ghat.data_ptr(), sums3.data_ptr<float>(), R, (int)C, rs)
+    if (go2p) REDUCE_DUAL(true);
+    else REDUCE_DUAL(false);
+#undef REDUCE_DUAL
+    CHECK_CUDA_OK();
+    k3 = bn_bwd_coeffs(sums3, weight3, mean3, invstd3, R, C);
+    kd = bn_bwd_coeffs(sums_d, weight_d, mean_d, invstd_d, R, C);
+    long total_vec = R * C / VEC;
+    int agrid = amd_grid(total_vec);
+    BNDualBwdSide<devT> as{(const devT*)x_d.const_data_ptr(),
+                           (devT*)gx_d.data_ptr(), kd.A.data_ptr<float>(),
+                           kd.Bc.data_ptr<float>(), kd.Dc.data_ptr<float>()};
+    bn_bwd_apply_kernel<devT, VEC, 0, false, true, true>
+        <<<agrid, AMD_TPB, 0, stream>>>(
+            (const devT*)x3.const_data_ptr(),
+            (const devT*)ghat.const_data_ptr(), (devT*)gx3.data_ptr(),
+            nullptr, k3.A.data_ptr<float>(), k3.Bc.data_ptr<float>(),
+            k3.Dc.data_ptr<float>(), nullptr, nullptr, total_vec, (int)C, as);
+    CHECK_CUDA_OK();
+  });
+  return {gx3, k3.gw, k3.gb, gx_d, kd.gw, kd.gb};
 }
 
 at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
@@ -642,7 +952,8 @@ at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
 }
 
 std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
-                                       at::Tensor y, at::Tensor weight,
+                                       std::optional<at::Tensor> y,
+                                       at::Tensor weight,
                                        at::Tensor mean, at::Tensor invstd,
                                        bool relu, bool need_ghat,
                                        std::optional<at::Tensor> scale,
@@ -666,11 +977,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   auto opts = x.options().dtype(at::kFloat);
   const int rgrid = bn_reduce_grid(R, C);
   auto sums = at::empty({rgrid, 2 * C}, opts);
-  auto gw = at::empty({C}, opts);
-  auto gb = at::empty({C}, opts);
-  auto A = at::empty({C}, opts);
-  auto Bc = at::empty({C}, opts);
-  auto Dc = at::empty({C}, opts);
+  BNBwdCoeffs k;
   auto gx = at::empty_like(x);
   const bool affine_mask = relu && !need_ghat && scale && shift;
   // grad_out2 (rerouted residual gradient) forces the ghat-writing path so
@@ -692,7 +999,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
       <<<rgrid, AMD_TPB, 0, stream>>>(                                      \
           (const devT*)x.const_data_ptr(),                                  \
           (const devT*)grad_out.const_data_ptr(), go2p,                     \
-          (const devT*)y.const_data_ptr(), mean.data_ptr<float>(),          \
+          yp, mean.data_ptr<float>(),                                       \
           invstd.data_ptr<float>(), scp, shp,                               \
           WG_ ? (devT*)ghat.data_ptr() : nullptr,                           \
           sums.data_ptr<float>(), R, (int)C)
@@ -708,6 +1015,12 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
           sums.data_ptr<float>(), R, (int)C)
     const unsigned char* mkp = (relu_mask && relu_mask->numel())
         ? relu_mask->data_ptr<unsigned char>() : nullptr;
+    // only the MASK 1 reduce dereferences y (the affine-mask and bitmask
+    // forms never do, so their callers need not keep y alive)
+    TORCH_CHECK(y.has_value() || !mask_y || mkp,
+                "batch_norm_bwd: y is required to mask a relu+addend BN "
+                "that saved no relu_mask");
+    const devT* yp = y ? (const devT*)y->const_data_ptr() : nullptr;
     if (mask_y && mkp && go2p) REDUCE3(true);
     else if (mask_y && mkp) REDUCE3(false);
     else if (mask_y && go2p) REDUCE(1, true, true);
@@ -718,22 +1031,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
 #undef REDUCE
 #undef REDUCE3
     CHECK_CUDA_OK();
-    const int slots = bn_collapse_slots(rgrid);
-    auto sums2 = at::empty({slots, 2 * C}, opts);
-    {
-      int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
-      bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
-          sums.data_ptr<float>(), sums2.data_ptr<float>(), rgrid,
-          (int)(2 * C), slots);
-      CHECK_CUDA_OK();
-    }
-    int fgrid = (int)((C + 63) / 64);
-    bn_bwd_finalize_kernel<<<fgrid, AMD_TPB, 0, stream>>>(
-        sums2.data_ptr<float>(), slots, weight.data_ptr<float>(),
-        mean.data_ptr<float>(), invstd.data_ptr<float>(),
-        gw.data_ptr<float>(), gb.data_ptr<float>(), A.data_ptr<float>(),
-        Bc.data_ptr<float>(), Dc.data_ptr<float>(), R, (int)C);
-    CHECK_CUDA_OK();
+    k = bn_bwd_coeffs(sums, weight, mean, invstd, R, C);
     long total_vec = R * C / VEC;
     int agrid = amd_grid(total_vec);
     size_t smem = (affine_mask ? 5 : 3) * C * sizeof(float);
@@ -746,13 +1044,13 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   bn_bwd_apply_kernel<devT, VEC, MASK_, false, true>                        \
       <<<agrid, AMD_TPB, smem, stream>>>(                                   \
           (const devT*)x.const_data_ptr(), go_in, (devT*)gx.data_ptr(),     \
-          nullptr, A.data_ptr<float>(), Bc.data_ptr<float>(),               \
-          Dc.data_ptr<float>(), scp, shp, total_vec, (int)C)
+          nullptr, k.A.data_ptr<float>(), k.Bc.data_ptr<float>(),           \
+          k.Dc.data_ptr<float>(), scp, shp, total_vec, (int)C)
     if (affine_mask) BAPPLY(2);
     else BAPPLY(0);
 #undef BAPPLY
     CHECK_CUDA_OK();
   });
   if (!ghat.defined()) ghat = grad_out;  // placeholder (no addend path)
-  return {gx, gw, gb, ghat};
+  return {gx, k.gw, k.gb, ghat};
 }

@@ -40,8 +40,25 @@ at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
                                std::optional<at::Tensor> addend);
+std::vector<at::Tensor> batch_norm_train_stats(
+    at::Tensor x, std::optional<at::Tensor> parts, at::Tensor weight,
+    at::Tensor bias, at::Tensor running_mean, at::Tensor running_var,
+    double momentum, double eps);
+std::vector<at::Tensor> batch_norm_dual_fwd_train(
+    at::Tensor x3, at::Tensor x_d, std::optional<at::Tensor> parts3,
+    std::optional<at::Tensor> parts_d, at::Tensor weight3, at::Tensor bias3,
+    at::Tensor running_mean3, at::Tensor running_var3, double momentum3,
+    double eps3, at::Tensor weight_d, at::Tensor bias_d,
+    at::Tensor running_mean_d, at::Tensor running_var_d, double momentum_d,
+    double eps_d);
+std::vector<at::Tensor> batch_norm_dual_bwd(
+    at::Tensor x3, at::Tensor x_d, at::Tensor grad_out,
+    std::optional<at::Tensor> grad_out2, at::Tensor relu_mask,
+    at::Tensor weight3, at::Tensor mean3, at::Tensor invstd3,
+    at::Tensor weight_d, at::Tensor mean_d, at::Tensor invstd_d);
 std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
-                                       at::Tensor y, at::Tensor weight,
+                                       std::optional<at::Tensor> y,
+                                       at::Tensor weight,
                                        at::Tensor mean, at::Tensor invstd,
                                        bool relu, bool need_ghat,
                                        std::optional<at::Tensor> scale,
@@ -97,7 +114,9 @@ at::Tensor conv_generic_dgrad(at::Tensor dy2d, at::Tensor w2p, long Nn,
                               long pad);
 
 // pool.hip
-std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x);
+std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x,
+                                            std::optional<at::Tensor> scale,
+                                            std::optional<at::Tensor> shift);
 at::Tensor max_pool_3x3_s2_bwd(at::Tensor grad_y, at::Tensor idx, long H,
                                long W);
 at::Tensor global_avg_pool_fwd(at::Tensor x);
@@ -126,6 +145,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("eps"),
         py::arg("relu"), py::arg("addend") = std::nullopt);
+  m.def("batch_norm_train_stats", &batch_norm_train_stats);
+  m.def("batch_norm_dual_fwd_train", &batch_norm_dual_fwd_train);
+  m.def("batch_norm_dual_bwd", &batch_norm_dual_bwd);
   m.def("batch_norm_bwd", &batch_norm_bwd, py::arg("x"), py::arg("grad_out"),
         py::arg("y"), py::arg("weight"), py::arg("mean"), py::arg("invstd"),
         py::arg("relu"), py::arg("need_ghat"),
@@ -161,7 +183,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_generic_fwd", &conv_generic_fwd);
   m.def("conv_generic_wgrad", &conv_generic_wgrad);
   m.def("conv_generic_dgrad", &conv_generic_dgrad);
-  m.def("max_pool_3x3_s2_fwd", &max_pool_3x3_s2_fwd);
+  m.def("max_pool_3x3_s2_fwd", &max_pool_3x3_s2_fwd, py::arg("x"),
+        py::arg("scale") = std::nullopt, py::arg("shift") = std::nullopt);
   m.def("max_pool_3x3_s2_bwd", &max_pool_3x3_s2_bwd);
   m.def("global_avg_pool_fwd", &global_avg_pool_fwd);
   m.def("global_avg_pool_bwd", &global_avg_pool_bwd);

@@ -6,11 +6,26 @@
 
 namespace {
 
-template <typename T, int VEC>
+// BNRELU (stem): x is the RAW stem-conv output and each tap is formed as
+// T(max(scale*x + shift, 0)) before the compare — the rounded post-ReLU
+// value the separate BN apply used to write — so the largest activation of
+// the net (112x112x64) is never written or read back; output and argmax
+// codes are those of the two-kernel path.
+template <typename T, int VEC, bool BNRELU = false>
 __global__ void __launch_bounds__(AMD_TPB)
 maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
                    unsigned char* __restrict__ idx, long N, int H, int W,
-                   int C, int Ho, int Wo) {
+                   int C, int Ho, int Wo,
+                   const float* __restrict__ scale = nullptr,
+                   const float* __restrict__ shift = nullptr) {
+  extern __shared__ float sm[];  // BNRELU: [2][C]
+  if (BNRELU) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      sm[c] = scale[c];
+      sm[C + c] = shift[c];
+    }
+    __syncthreads();
+  }
   const int gpr = C / VEC;
   const long total = N * Ho * Wo * gpr;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -43,6 +58,9 @@ maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
           float v = to_f32(xv.v[k]);
+          if (BNRELU)
+            v = to_f32(from_f32<T>(
+                fmaxf(sm[c0 + k] * v + sm[C + c0 + k], 0.f)));
           if (v > best[k]) {
             best[k] = v;
             bidx[k] = (unsigned char)(kh * 3 + kw);
@@ -165,8 +183,19 @@ static void check_nhwc4(const at::Tensor& x) {
 
 }  // namespace
 
-std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x) {
+// scale/shift given: the stem BN+ReLU is applied per tap inside the pool
+std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x,
+                                            std::optional<at::Tensor> scale,
+                                            std::optional<at::Tensor> shift) {
   check_nhwc4(x);
+  TORCH_CHECK(scale.has_value() == shift.has_value(),
+              "scale and shift come together");
+  const bool bnrelu = scale.has_value();
+  if (bnrelu)
+    TORCH_CHECK(scale->numel() == x.size(1) && shift->numel() == x.size(1) &&
+                    scale->scalar_type() == at::kFloat &&
+                    shift->scalar_type() == at::kFloat,
+                "scale/shift must be [C] fp32");
   const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const long Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   auto y = at::empty({N, C, Ho, Wo},
@@ -183,11 +212,19 @@ std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x) {
         constexpr int VEC = 16 / sizeof(devT);
         TORCH_CHECK(C % VEC == 0);
         long total = N * Ho * Wo * (C / VEC);
-        maxpool_fwd_kernel<devT, VEC>
-            <<<amd_grid(total), AMD_TPB, 0, stream>>>(
-                (const devT*)x.const_data_ptr(), (devT*)y.data_ptr(),
-                (unsigned char*)idx.data_ptr(), N, (int)H, (int)W, (int)C,
-                (int)Ho, (int)Wo);
+        if (bnrelu)
+          maxpool_fwd_kernel<devT, VEC, true>
+              <<<amd_grid(total), AMD_TPB, 2 * C * sizeof(float), stream>>>(
+                  (const devT*)x.const_data_ptr(), (devT*)y.data_ptr(),
+                  (unsigned char*)idx.data_ptr(), N, (int)H, (int)W, (int)C,
+                  (int)Ho, (int)Wo, scale->data_ptr<float>(),
+                  shift->data_ptr<float>());
+        else
+          maxpool_fwd_kernel<devT, VEC>
+              <<<amd_grid(total), AMD_TPB, 0, stream>>>(
+                  (const devT*)x.const_data_ptr(), (devT*)y.data_ptr(),
+                  (unsigned char*)idx.data_ptr(), N, (int)H, (int)W, (int)C,
+                  (int)Ho, (int)Wo);
         CHECK_CUDA_OK();
       });
   return {y, idx};

@@ -12,6 +12,7 @@ uses custom autograd.Functions over the extension.
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -20,7 +21,8 @@ import torch.nn.functional as F
 from ._ext import require_ext, use_ext_for
 from .conv import GradCell
 
-__all__ = ["batch_norm", "bn_add_relu", "max_pool_3x3_s2", "global_avg_pool"]
+__all__ = ["batch_norm", "bn_add_relu", "bn_add_relu_downsample",
+           "bn_relu_max_pool", "max_pool_3x3_s2", "global_avg_pool"]
 
 
 class _BNFunction(torch.autograd.Function):
@@ -120,6 +122,94 @@ def bn_add_relu(x: torch.Tensor, bn, addend: torch.Tensor) -> torch.Tensor:
     return batch_norm(x, bn, relu=True, addend=addend)
 
 
+class _BNDualFunction(torch.autograd.Function):
+    """Downsample-block tail: relu(bn3(x3) + bn_d(x_d)) with the downsample
+    BN's output never written to memory, and one backward reduce + one
+    backward apply serving both BNs (they share ghat).  Bitwise equal to
+    _BNFunction(bn_d) feeding _BNFunction(bn3, addend)."""
+
+    @staticmethod
+    def forward(ctx, x3, x_d, weight3, bias3, running_mean3, running_var3,
+                momentum3, eps3, weight_d, bias_d, running_mean_d,
+                running_var_d, momentum_d, eps_d, parts3, parts_d, res_cell):
+        e = require_ext()
+        y, mean3, invstd3, mean_d, invstd_d, mask = \
+            e.batch_norm_dual_fwd_train(
+                x3, x_d, parts3, parts_d,
+                weight3, bias3, running_mean3, running_var3,
+                float(momentum3), float(eps3),
+                weight_d, bias_d, running_mean_d, running_var_d,
+                float(momentum_d), float(eps_d))
+        ctx.save_for_backward(x3, x_d, weight3, mean3, invstd3, weight_d,
+                              mean_d, invstd_d, mask)
+        # same mailbox as _BNFunction block tails: the next block's rerouted
+        # shortcut gradient arrives as a second go operand of the reduce
+        ctx.res_cell = res_cell
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (x3, x_d, weight3, mean3, invstd3, weight_d, mean_d, invstd_d,
+         mask) = ctx.saved_tensors
+        e = require_ext()
+        go2 = None
+        cell = getattr(ctx, "res_cell", None)
+        if cell is not None and cell.g is not None:
+            go2 = cell.g.contiguous(memory_format=torch.channels_last)
+            cell.g = None
+        gx3, gw3, gb3, gx_d, gw_d, gb_d = e.batch_norm_dual_bwd(
+            x3, x_d, grad_out.contiguous(memory_format=torch.channels_last),
+            go2, mask, weight3, mean3, invstd3, weight_d, mean_d, invstd_d)
+        return (gx3, gx_d, gw3, gb3, None, None, None, None, gw_d, gb_d,
+                None, None, None, None, None, None, None)
+
+
+def _dsfuse_enabled() -> bool:
+    """AMDTRAIN_DSFUSE=0 restores the separate downsample-BN passes."""
+    return os.environ.get("AMDTRAIN_DSFUSE", "1") == "1"
+
+
+def _stemfuse_enabled() -> bool:
+    """AMDTRAIN_STEMFUSE=0 restores the separate stem BN+ReLU apply."""
+    return os.environ.get("AMDTRAIN_STEMFUSE", "1") == "1"
+
+
+def _vec_ok(x: torch.Tensor, max_groups: int) -> bool:
+    """The kernels' channel guards: pow2 C, whole 16-byte packs, and at most
+    ``max_groups`` packs per row."""
+    C = x.size(1)
+    vec = 16 // x.element_size()
+    return (C & (C - 1)) == 0 and C % vec == 0 and C // vec <= max_groups
+
+
+def bn_add_relu_downsample(x3: torch.Tensor, bn3, x_d: torch.Tensor,
+                           bn_d) -> torch.Tensor:
+    """relu(bn3(x3) + bn_d(x_d)) — the tail of a residual block whose
+    shortcut is conv -> BN; ``x_d`` is the raw downsample-conv output.  One
+    dual-BN kernel per pass in training on GPU; otherwise (eval, CPU,
+    extension off, AMDTRAIN_DSFUSE=0, or a channel count the dual kernels
+    do not take, e.g. fp32 C=2048) the two-BN composition."""
+    if (bn3.training and bn_d.training and _dsfuse_enabled()
+            and use_ext_for(x3) and x3.shape == x_d.shape
+            and x3.dtype == x_d.dtype and _vec_ok(x3, 256)):
+        for bn in (bn_d, bn3):
+            if bn.track_running_stats and bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+        parts3 = getattr(x3, "_amdtrain_bn_stats", None)
+        parts_d = getattr(x_d, "_amdtrain_bn_stats", None)
+        cell = GradCell()
+        out = _BNDualFunction.apply(
+            x3.contiguous(memory_format=torch.channels_last),
+            x_d.contiguous(memory_format=torch.channels_last),
+            bn3.weight, bn3.bias, bn3.running_mean, bn3.running_var,
+            bn3.momentum, bn3.eps, bn_d.weight, bn_d.bias,
+            bn_d.running_mean, bn_d.running_var, bn_d.momentum, bn_d.eps,
+            parts3, parts_d, cell)
+        out._amdtrain_next_cell = cell
+        return out
+    return bn_add_relu(x3, bn3, batch_norm(x_d, bn_d))
+
+
 class _MaxPool3x3S2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -145,6 +235,52 @@ def max_pool_3x3_s2(x: torch.Tensor) -> torch.Tensor:
     if use_ext_for(x):
         return _MaxPool3x3S2.apply(x.contiguous(memory_format=torch.channels_last))
     return F.max_pool2d(x, kernel_size=3, stride=2, padding=1)
+
+
+class _BNReLUMaxPool(torch.autograd.Function):
+    """Stem: max_pool_3x3_s2(relu(bn(x))) with BN+ReLU applied per tap inside
+    the pool kernel, so the 112x112x64 activation is neither written nor
+    saved.  Backward is the pool gather followed by the BN backward in its
+    affine-mask form, which recomputes the ReLU mask from scale/shift."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps, parts):
+        e = require_ext()
+        mean, invstd, scale, shift = e.batch_norm_train_stats(
+            x, parts, weight, bias, running_mean, running_var,
+            float(momentum), float(eps))
+        y, idx = e.max_pool_3x3_s2_fwd(x, scale, shift)
+        ctx.save_for_backward(x, idx, weight, mean, invstd, scale, shift)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, idx, weight, mean, invstd, scale, shift = ctx.saved_tensors
+        e = require_ext()
+        gp = e.max_pool_3x3_s2_bwd(
+            grad_out.contiguous(memory_format=torch.channels_last), idx,
+            int(x.size(2)), int(x.size(3)))
+        grad_x, grad_w, grad_b, _ = e.batch_norm_bwd(
+            x, gp, None, weight, mean, invstd, True, False, scale, shift,
+            None, None)
+        return grad_x, grad_w, grad_b, None, None, None, None, None
+
+
+def bn_relu_max_pool(x: torch.Tensor, bn) -> torch.Tensor:
+    """max_pool_3x3_s2(relu(bn(x))) — the ResNet stem after conv1.  One
+    fused pool kernel in training on GPU; otherwise (eval, CPU, extension
+    off, AMDTRAIN_STEMFUSE=0) the two-op composition."""
+    if (bn.training and _stemfuse_enabled() and use_ext_for(x)
+            and _vec_ok(x, 512)):
+        if bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        parts = getattr(x, "_amdtrain_bn_stats", None)
+        return _BNReLUMaxPool.apply(
+            x.contiguous(memory_format=torch.channels_last), bn.weight,
+            bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+            parts)
+    return max_pool_3x3_s2(batch_norm(x, bn, relu=True))
 
 
 class _GlobalAvgPool(torch.autograd.Function):
