@@ -31,7 +31,8 @@ from ..ops import fused as OF
 
 import os
 
-from ..ops.conv import AmdConv2d, GradCell, ResidualGradTap  # noqa: F401
+from ..ops.conv import (AmdConv2d, GradCell, ResidualGradTap,  # noqa: F401
+                        tap_residual)
 from ..ops.linear import AmdLinear
 
 
@@ -107,7 +108,7 @@ class BasicBlock(nn.Module):
         out = self.conv2(out)
         if cell is not None:
             cell.armed = True
-            identity = ResidualGradTap.apply(x, cell)
+            identity = tap_residual(x, cell)
         if self.downsample is not None:
             return _shortcut_tail(out, self.bn2, self.downsample, identity)
         return OF.bn_add_relu(out, self.bn2, identity)
@@ -150,7 +151,7 @@ class Bottleneck(nn.Module):
         out = self.conv3(out)
         if cell is not None:
             cell.armed = True
-            identity = ResidualGradTap.apply(x, cell)
+            identity = tap_residual(x, cell)
         if self.downsample is not None:
             return _shortcut_tail(out, self.bn3, self.downsample, identity)
         return OF.bn_add_relu(out, self.bn3, identity)

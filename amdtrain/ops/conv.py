@@ -42,12 +42,24 @@ class GradCell:
     """Shared mailbox between ResidualGradTap and the producing block-tail
     _BNFunction (fused.py).  A plain class (NOT a dict):
     torch.amp.custom_fwd(cast_inputs=...) deep-copies dict arguments while
-    casting, which would silently disconnect the mailbox."""
-    __slots__ = ("armed", "g")
+    casting, which would silently disconnect the mailbox.
+
+    ``compact_ok`` is set by a producer whose backward can read a stride-2
+    1x1 conv's dgrad in its compact ``[N*ho*wo, C]`` form; the conv then
+    leaves that tensor in ``g`` with ``meta = (n, h, w, ho, wo)`` instead of
+    scattering it to full resolution."""
+    __slots__ = ("armed", "g", "compact_ok", "meta")
 
     def __init__(self):
         self.armed = False
         self.g = None
+        self.compact_ok = False
+        self.meta = None
+
+
+def _dsgrad_compact_enabled() -> bool:
+    """AMDTRAIN_DSGRAD_COMPACT=0 restores the scatter_rows_x2 pass."""
+    return os.environ.get("AMDTRAIN_DSGRAD_COMPACT", "1") == "1"
 
 
 class ResidualGradTap(torch.autograd.Function):
@@ -65,19 +77,35 @@ class ResidualGradTap(torch.autograd.Function):
     16 B vectorized stream as its other inputs.  Safety latch: the grad is
     stashed ONLY when the producing BN armed the cell; any fallback keeps
     plain autograd accumulation.
+
+    A stride-2 downsample conv fed by the tap may already have left its
+    compact dgrad in the cell (see _Conv1x1.backward); it then returns no
+    input gradient and the tap sees ``None``.
     """
 
     @staticmethod
     def forward(ctx, z: torch.Tensor, cell: "GradCell"):
         ctx.cell = cell
+        ctx.set_materialize_grads(False)
         return z.view_as(z)
 
     @staticmethod
-    def backward(ctx, grad: torch.Tensor):
+    def backward(ctx, grad):
+        if grad is None:
+            return None, None
         if ctx.cell.armed:
             ctx.cell.g = grad
+            ctx.cell.meta = None
             return None, None
         return grad, None
+
+
+def tap_residual(x: torch.Tensor, cell: "GradCell") -> torch.Tensor:
+    """ResidualGradTap on ``x``; the result also carries the cell so a
+    downsample conv consuming it can find the mailbox."""
+    out = ResidualGradTap.apply(x, cell)
+    out._amdtrain_tap_cell = cell
+    return out
 
 
 class _Conv1x1(torch.autograd.Function):
@@ -88,7 +116,8 @@ class _Conv1x1(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
+                cell=None):
         e = require_ext()
         n, cin, h, w = x.shape
         cout = weight.shape[0]
@@ -96,6 +125,7 @@ class _Conv1x1(torch.autograd.Function):
         x2d = _rows(xc)
         w2d = weight.reshape(cout, cin)
         stats = None
+        ctx.cell = cell
         if stride > 1:
             # even-row gather happens inside the A staging (no copy); the
             # full x2d is saved — it is the same tensor the sibling conv of
@@ -129,8 +159,20 @@ class _Conv1x1(torch.autograd.Function):
         wT = e.transpose_2d(w2d)                      # [Cin, Cout]
         dx2d = e.gemm_bt(gy2d, wT, False)             # [R_sub, Cin] bf16
         if stride > 1:
-            # fused zero+scatter (one write pass; stride-2 only in ResNet)
-            dx = e.scatter_rows_x2(dx2d, n, h, w, ho, wo)
+            cell = ctx.cell
+            if (stride == 2 and cell is not None and cell.armed
+                    and cell.compact_ok):
+                # the producing block tail's reduce reads the compact dgrad
+                # at the even positions itself: no full-resolution tensor
+                # that is 3/4 zeros.  It travels out of band (autograd
+                # would reject its shape as this conv's input gradient).
+                cell.g = dx2d
+                cell.meta = (n, h, w, ho, wo)
+                dx = None
+            else:
+                # fused zero+scatter (one write pass; stride-2 only in
+                # ResNet)
+                dx = e.scatter_rows_x2(dx2d, n, h, w, ho, wo)
             dw = e.tn2_wgrad(gy2d, x2d, 1, n, h, w, stride, 1) \
                 if _wgrad2_enabled() \
                 else e.gemm_tn_strided(gy2d, x2d, n, h, w, stride)
@@ -138,12 +180,15 @@ class _Conv1x1(torch.autograd.Function):
             dx = dx2d.view(n, ho, wo, cin).permute(0, 3, 1, 2)
             dw = e.tn2_wgrad(gy2d, x2d) if _wgrad2_enabled() \
                 else e.gemm_tn(gy2d, x2d, 0)
-        return dx, dw.reshape(cout, cin, 1, 1), None
+        return dx, dw.reshape(cout, cin, 1, 1), None, None
 
 
 def conv1x1_mfma(x: torch.Tensor, weight: torch.Tensor,
                  stride: int = 1) -> torch.Tensor:
-    y, stats = _Conv1x1.apply(x, weight, stride)
+    # a stride-2 conv fed by a ResidualGradTap is the downsample conv: it
+    # may hand its compact dgrad to the tap's mailbox
+    cell = getattr(x, "_amdtrain_tap_cell", None) if stride == 2 else None
+    y, stats = _Conv1x1.apply(x, weight, stride, cell)
     if stats.numel():
         y._amdtrain_bn_stats = stats
     return y

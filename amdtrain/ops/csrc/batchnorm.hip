@@ -15,6 +15,9 @@
 // sums live in registers (no LDS atomics in the hot loop), then one LDS
 // phase-reduction per block and one global atomicAdd per channel per block.
 // All ResNet channel counts (64..2048) hit this register path.
+#include <cstdlib>
+#include <cstring>
+
 #include "common.h"
 
 namespace {
@@ -47,8 +50,110 @@ struct BNDualSide {
   float* out = nullptr;
 };
 
+// Gradient operands that are a pure gather of a smaller tensor are formed
+// in the consuming BN kernel instead of being written out and read back:
+//  GSRC_POOL:    go is the stem max pool's input gradient — per element the
+//                fp32 sum, in (ho, wo) order, of the <= 4 pool-output
+//                gradients whose argmax code selects it, rounded through T
+//                like the tensor maxpool_bwd_kernel wrote.  With gy2 (the
+//                pool output's second consumer) each window contributes
+//                T(gy + gy2), the value the eager add produced.
+//  GSRC_COMPACT: goB is the [N,Hs,Ws,C] dgrad of a stride-2 1x1 conv; row
+//                (n,h,w) reads (n,h/2,w/2) when h and w are even, else 0 —
+//                the tensor scatter_rows_x2 wrote.
+constexpr int GSRC_NONE = 0, GSRC_POOL = 1, GSRC_COMPACT = 2;
+
+template <typename T>
+struct BNGradSrc {
+  const T* gy = nullptr;
+  const T* gy2 = nullptr;
+  const unsigned char* idx = nullptr;
+  int H = 0, W = 0, Hs = 0, Ws = 0;
+};
+
+// (n,h,w) of a row, decoded once per thread and advanced incrementally
+// (H, W are not powers of two: no 64-bit divide per row)
+struct RowPos {
+  int n, h, w;
+};
+
+__device__ __forceinline__ RowPos row_decode(long r, int H, int W) {
+  RowPos p;
+  p.w = (int)(r % W);
+  r /= W;
+  p.h = (int)(r % H);
+  p.n = (int)(r / H);
+  return p;
+}
+
+// p += d for d.w < W, d.h < H (one carry each)
+__device__ __forceinline__ void row_advance(RowPos& p, const RowPos& d, int H,
+                                            int W) {
+  p.w += d.w;
+  int c = p.w >= W;
+  if (c) p.w -= W;
+  p.h += d.h + c;
+  c = p.h >= H;
+  if (c) p.h -= H;
+  p.n += d.n + c;
+}
+
+template <typename T, int VEC>
+__device__ __forceinline__ Pack<T, VEC> pool_grad_gather(
+    const BNGradSrc<T>& s, const RowPos& p, int C, int c0) {
+  float acc[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  // windows (ho,wo) containing (h,w): ho in {h/2, (h+1)/2}, ascending,
+  // exactly the loop maxpool_bwd_kernel runs
+  const int nh = ((p.h & 1) && (p.h + 1) / 2 < s.Hs) ? 2 : 1;
+  const int nw = ((p.w & 1) && (p.w + 1) / 2 < s.Ws) ? 2 : 1;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    if (a >= nh) continue;
+    const int ho = p.h / 2 + a;
+    const int kh = p.h - (ho * 2 - 1);
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      if (b >= nw) continue;
+      const int wo = p.w / 2 + b;
+      const int kw = p.w - (wo * 2 - 1);
+      const unsigned char code = (unsigned char)(kh * 3 + kw);
+      const long obase = (((long)p.n * s.Hs + ho) * s.Ws + wo) * C + c0;
+      Pack<unsigned char, VEC> iv =
+          *(const Pack<unsigned char, VEC>*)(s.idx + obase);
+      Pack<T, VEC> gv = *(const Pack<T, VEC>*)(s.gy + obase);
+      if (s.gy2 != nullptr) {
+        Pack<T, VEC> g2 = *(const Pack<T, VEC>*)(s.gy2 + obase);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k)
+          gv.v[k] = from_f32<T>(to_f32(gv.v[k]) + to_f32(g2.v[k]));
+      }
+#pragma unroll
+      for (int k = 0; k < VEC; ++k)
+        if (iv.v[k] == code) acc[k] += to_f32(gv.v[k]);
+    }
+  }
+  Pack<T, VEC> out;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) out.v[k] = from_f32<T>(acc[k]);
+  return out;
+}
+
+template <typename T, int VEC>
+__device__ __forceinline__ Pack<T, VEC> compact_grad_gather(
+    const BNGradSrc<T>& s, const RowPos& p, int C, int c0) {
+  if (((p.h | p.w) & 1) == 0)
+    return *(const Pack<T, VEC>*)(
+        s.gy + (((long)p.n * s.Hs + p.h / 2) * s.Ws + p.w / 2) * C + c0);
+  Pack<T, VEC> z;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) z.v[k] = from_f32<T>(0.f);
+  return z;
+}
+
 template <typename T, int VEC, bool BWD, int MASK, bool WG, bool GO2,
-          bool DUAL = false>
+          bool DUAL = false, int GSRC = GSRC_NONE>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
                  const T* __restrict__ goB, const T* __restrict__ y,
@@ -57,8 +162,10 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
                  const float* __restrict__ scale,
                  const float* __restrict__ shift, T* __restrict__ ghat_out,
                  float* __restrict__ out, long R, int C,
-                 BNDualSide<T> ds = {}) {
+                 BNDualSide<T> ds = {}, BNGradSrc<T> gs = {}) {
   static_assert(!DUAL || (BWD && WG), "DUAL rides the ghat-writing bwd pass");
+  static_assert(GSRC == GSRC_NONE || BWD, "gather operands are gradients");
+  static_assert(GSRC != GSRC_COMPACT || GO2, "the compact operand is go2");
   const int t = threadIdx.x;
   const int gpr = C / VEC;  // channel-groups per row
   // rows are split across blocks
@@ -93,15 +200,31 @@ bn_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
         }
       }
     }
+    RowPos pos{0, 0, 0};
+    if (GSRC != GSRC_NONE && r0 + phase < r1)
+      pos = row_decode(r0 + phase, gs.H, gs.W);
     for (long r = r0 + phase; r < r1; r += rstep) {
       const long base = r * C + c0;
       Pack<T, VEC> xv = *(const Pack<T, VEC>*)(x + base);
       Pack<T, VEC> gv, gv2, yv, gh, dv;
       unsigned int mbits = 0;
       if (BWD) {
-        gv = *(const Pack<T, VEC>*)(go + base);
+        if (GSRC == GSRC_POOL) gv = pool_grad_gather<T, VEC>(gs, pos, C, c0);
+        else gv = *(const Pack<T, VEC>*)(go + base);
         if (DUAL) dv = *(const Pack<T, VEC>*)(ds.x + base);
-        if (GO2) gv2 = *(const Pack<T, VEC>*)(goB + base);
+        if (GSRC == GSRC_COMPACT)
+          gv2 = compact_grad_gather<T, VEC>(gs, pos, C, c0);
+        else if (GO2) gv2 = *(const Pack<T, VEC>*)(goB + base);
+        if (GSRC != GSRC_NONE) {  // rstep may exceed W at small shapes
+          pos.w += rstep;
+          while (pos.w >= gs.W) {
+            pos.w -= gs.W;
+            if (++pos.h == gs.H) {
+              pos.h = 0;
+              ++pos.n;
+            }
+          }
+        }
         if (MASK == 1) yv = *(const Pack<T, VEC>*)(y + base);
         if (MASK == 3)
           mbits = ((const unsigned char*)y)[base / VEC];
@@ -323,7 +446,7 @@ __global__ void bn_finalize_eval_kernel(
 // Its four coefficient sets stay in registers (measured +0.7% end to end
 // over [4][C] in LDS).
 template <typename T, int VEC, bool RELU, bool HAS_ADD, bool POW2,
-          bool DUAL = false>
+          bool DUAL = false, bool REGC = DUAL>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
                 T* __restrict__ y, unsigned char* __restrict__ mask,
@@ -332,22 +455,27 @@ bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
                 const float* __restrict__ scale_d = nullptr,
                 const float* __restrict__ shift_d = nullptr) {
   static_assert(!DUAL || (HAS_ADD && POW2), "DUAL normalizes the addend");
-  extern __shared__ float sm[];  // [2][C] (unused by DUAL)
+  static_assert(!DUAL || REGC, "DUAL keeps its coefficients in registers");
+  static_assert(!REGC || POW2, "REGC needs a pow2 channel-group count");
+  extern __shared__ float sm[];  // [2][C] (unused by REGC)
   const int gpr = C / VEC;
   const long stride = (long)gridDim.x * blockDim.x;
-  // DUAL: the host admits only pow2 C/VEC <= blockDim, so the grid stride
+  // REGC: the host admits only pow2 C/VEC <= blockDim, so the grid stride
   // is a multiple of C/VEC and a thread keeps ONE channel group for the
-  // whole loop — its four coefficient sets live in registers, not LDS.
+  // whole loop — its two (DUAL: four) coefficient sets live in registers,
+  // not LDS.
   float rs[VEC], rb[VEC], rsd[VEC], rbd[VEC];
-  if (DUAL) {
+  if (REGC) {
     const int cf =
         (int)(((long)blockIdx.x * blockDim.x + threadIdx.x) & (gpr - 1)) * VEC;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       rs[k] = scale[cf + k];
       rb[k] = shift[cf + k];
-      rsd[k] = scale_d[cf + k];
-      rbd[k] = shift_d[cf + k];
+      if (DUAL) {
+        rsd[k] = scale_d[cf + k];
+        rbd[k] = shift_d[cf + k];
+      }
     }
   } else {
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
@@ -373,7 +501,7 @@ bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
     unsigned int mb = 0, mb2 = 0;
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
-      float v = DUAL ? rs[k] * to_f32(xv.v[k]) + rb[k]
+      float v = REGC ? rs[k] * to_f32(xv.v[k]) + rb[k]
                      : sm[c0 + k] * to_f32(xv.v[k]) + sm[C + c0 + k];
       if (HAS_ADD) {
         float ze = to_f32(zv.v[k]);
@@ -385,7 +513,7 @@ bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
         v = fmaxf(v, 0.f);
       }
       yv.v[k] = from_f32<T>(v);
-      float v2 = DUAL ? rs[k] * to_f32(xv2.v[k]) + rb[k]
+      float v2 = REGC ? rs[k] * to_f32(xv2.v[k]) + rb[k]
                       : sm[c02 + k] * to_f32(xv2.v[k]) + sm[C + c02 + k];
       if (HAS_ADD) {
         float ze2 = to_f32(zv2.v[k]);
@@ -457,8 +585,26 @@ struct BNDualBwdSide {
   const float* Dc = nullptr;
 };
 
+// The LDS path's gx arithmetic with its contraction spelled out.  The
+// compiler is free to fuse either product of A*ghat + B*x + D into the FMA,
+// and it picks differently per kernel variant (MASK 0 fuses A*ghat, MASK 2
+// fuses B*x; with the coefficients in registers it flipped MASK 0), which
+// moves the last bit.  The register path pins the LDS path's choice.
+template <int MASK>
+__device__ __forceinline__ float bn_bwd_gx(float a, float b, float d,
+                                           float ge, float xe) {
+#pragma clang fp contract(off)
+  if (MASK == 2) return __builtin_fmaf(b, xe, a * ge) + d;
+  return __builtin_fmaf(a, ge, b * xe) + d;
+}
+
+// REGC (single BN, pow2 C/VEC <= blockDim): the same one-channel-group-per-
+// thread property lets the 3 (MASK 2: 5) coefficient sets live in registers
+// instead of LDS; the arithmetic is the LDS path's, so are the bits.
+// POOLGO (stem, REGC only): go is gathered from the max pool's gradient
+// (pool_grad_gather) instead of read from a materialized tensor.
 template <typename T, int VEC, int MASK, bool WRITE_GHAT, bool POW2,
-          bool DUAL = false>
+          bool DUAL = false, bool REGC = false, bool POOLGO = false>
 __global__ void __launch_bounds__(AMD_TPB)
 bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
                     T* __restrict__ gx,
@@ -466,9 +612,11 @@ bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
                     const float* __restrict__ Bc, const float* __restrict__ Dc,
                     const float* __restrict__ scale,
                     const float* __restrict__ shift, long total_vec, int C,
-                    BNDualBwdSide<T> ds = {}) {
+                    BNDualBwdSide<T> ds = {}, BNGradSrc<T> gs = {}) {
   static_assert(!DUAL || (MASK == 0 && POW2 && !WRITE_GHAT),
                 "DUAL consumes the materialized ghat");
+  static_assert(!REGC || (POW2 && !DUAL), "REGC is the single-BN form");
+  static_assert(!POOLGO || REGC, "POOLGO rides the register path");
   const int gpr = C / VEC;
   const long stride = (long)gridDim.x * blockDim.x;
   if (DUAL) {
@@ -516,6 +664,70 @@ bn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
       if (has2) {
         *(Pack<T, VEC>*)(gx + i2 * VEC) = out2;
         *(Pack<T, VEC>*)(ds.gx + i2 * VEC) = dout2;
+      }
+    }
+    return;
+  }
+  if (REGC) {
+    const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c0 = (int)(i0 & (gpr - 1)) * VEC;
+    float ra[VEC], rb[VEC], rd[VEC], rsc[VEC], rsh[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      ra[k] = A[c0 + k];
+      rb[k] = Bc[c0 + k];
+      rd[k] = Dc[c0 + k];
+      if (MASK == 2) {
+        rsc[k] = scale[c0 + k];
+        rsh[k] = shift[c0 + k];
+      }
+    }
+    // POOLGO: both streams' (n,h,w), advanced by two grid strides of rows
+    RowPos p1{0, 0, 0}, p2{0, 0, 0}, dstep{0, 0, 0};
+    if (POOLGO) {
+      const int lg = __builtin_ctz(gpr);
+      const long rstride = stride >> lg;  // stride is a multiple of gpr
+      if (i0 < total_vec) p1 = row_decode(i0 >> lg, gs.H, gs.W);
+      p2 = p1;
+      row_advance(p2, row_decode(rstride, gs.H, gs.W), gs.H, gs.W);
+      dstep = row_decode(2 * rstride, gs.H, gs.W);
+    }
+    for (long i = i0; i < total_vec; i += 2 * stride) {
+      const bool has2 = i + stride < total_vec;
+      const long i2 = has2 ? i + stride : i;  // clamp: loads stay in bounds
+      Pack<T, VEC> xv = *(const Pack<T, VEC>*)(x + i * VEC);
+      Pack<T, VEC> xv2 = *(const Pack<T, VEC>*)(x + i2 * VEC);
+      Pack<T, VEC> gv, gv2;
+      if (POOLGO) {
+        gv = pool_grad_gather<T, VEC>(gs, p1, C, c0);
+        gv2 = pool_grad_gather<T, VEC>(gs, has2 ? p2 : p1, C, c0);
+        row_advance(p1, dstep, gs.H, gs.W);
+        row_advance(p2, dstep, gs.H, gs.W);
+      } else {
+        gv = *(const Pack<T, VEC>*)(go + i * VEC);
+        gv2 = *(const Pack<T, VEC>*)(go + i2 * VEC);
+      }
+      Pack<T, VEC> out, gh, out2, gh2;
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        float xe = to_f32(xv.v[k]);
+        float ge = to_f32(gv.v[k]);
+        if (MASK == 2 && rsc[k] * xe + rsh[k] <= 0.f) ge = 0.f;
+        float v = bn_bwd_gx<MASK>(ra[k], rb[k], rd[k], ge, xe);
+        out.v[k] = from_f32<T>(v);
+        if (WRITE_GHAT) gh.v[k] = from_f32<T>(ge);
+        float xe2 = to_f32(xv2.v[k]);
+        float ge2 = to_f32(gv2.v[k]);
+        if (MASK == 2 && rsc[k] * xe2 + rsh[k] <= 0.f) ge2 = 0.f;
+        float v2 = bn_bwd_gx<MASK>(ra[k], rb[k], rd[k], ge2, xe2);
+        out2.v[k] = from_f32<T>(v2);
+        if (WRITE_GHAT) gh2.v[k] = from_f32<T>(ge2);
+      }
+      *(Pack<T, VEC>*)(gx + i * VEC) = out;
+      if (WRITE_GHAT) *(Pack<T, VEC>*)(ghat_out + i * VEC) = gh;
+      if (has2) {
+        *(Pack<T, VEC>*)(gx + i2 * VEC) = out2;
+        if (WRITE_GHAT) *(Pack<T, VEC>*)(ghat_out + i2 * VEC) = gh2;
       }
     }
     return;
@@ -591,6 +803,54 @@ static void dispatch_vec(const at::Tensor& x, F fn) {
         TORCH_CHECK(C / VEC <= 2 * AMD_TPB, "C too large: ", C);
         fn((devT*)nullptr, std::integral_constant<int, VEC>{});
       });
+}
+
+// AMDTRAIN_BN_REGCOEF=0 keeps the single-BN applies on the LDS coefficient
+// path (A/B switch; read per call so one process can compare both)
+static bool bn_regcoef_enabled() {
+  const char* v = std::getenv("AMDTRAIN_BN_REGCOEF");
+  return v == nullptr || std::strcmp(v, "1") == 0;
+}
+
+// forward apply shared by the train / from-parts / eval entries
+static void bn_apply_launch(const at::Tensor& x,
+                            const std::optional<at::Tensor>& addend,
+                            at::Tensor& y, const at::Tensor& mask,
+                            const at::Tensor& scale, const at::Tensor& shift,
+                            bool relu) {
+  const long C = x.size(1);
+  const long R = x.numel() / C;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dispatch_vec(x, [&](auto* tp, auto vec) {
+    using devT = std::remove_pointer_t<decltype(tp)>;
+    constexpr int VEC = decltype(vec)::value;
+    long total_vec = R * C / VEC;
+    int agrid = amd_grid(total_vec);
+    // one channel group per thread needs C/VEC (pow2) to divide the block
+    const bool regc = bn_regcoef_enabled() && C / VEC <= AMD_TPB;
+    size_t smem = regc ? 0 : 2 * C * sizeof(float);
+    const devT* zp =
+        addend ? (const devT*)addend->const_data_ptr() : nullptr;
+#define APPLY(RELU_, ADD_, REGC_)                                           \
+  bn_apply_kernel<devT, VEC, RELU_, ADD_, true, false, REGC_>               \
+      <<<agrid, AMD_TPB, smem, stream>>>(                                   \
+          (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),         \
+          mask.defined() ? mask.data_ptr<unsigned char>() : nullptr,        \
+          scale.data_ptr<float>(), shift.data_ptr<float>(), total_vec,      \
+          (int)C)
+#define APPLY_RC(RELU_, ADD_)                                               \
+  do {                                                                      \
+    if (regc) APPLY(RELU_, ADD_, true);                                     \
+    else APPLY(RELU_, ADD_, false);                                         \
+  } while (0)
+    if (relu && addend) APPLY_RC(true, true);
+    else if (relu) APPLY_RC(true, false);
+    else if (addend) APPLY_RC(false, true);
+    else APPLY_RC(false, false);
+#undef APPLY_RC
+#undef APPLY
+    CHECK_CUDA_OK();
+  });
 }
 
 static int bn_reduce_grid(long R, int C) {
@@ -692,6 +952,40 @@ static BNBwdCoeffs bn_bwd_coeffs(const at::Tensor& sums,
   return k;
 }
 
+// single-BN backward apply: the affine-mask form (MASK 2) when the forward's
+// scale/shift are given, else MASK 0.  pool != nullptr gathers go from the
+// stem pool gradient (register path only; the caller has checked C).
+template <typename devT, int VEC>
+static void bn_bwd_apply_launch(const devT* x, const devT* go, devT* gx,
+                                const BNBwdCoeffs& k, const float* scp,
+                                const float* shp, long R, long C,
+                                const BNGradSrc<devT>* pool) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const long total_vec = R * C / VEC;
+  const int agrid = amd_grid(total_vec);
+  const bool affine = scp != nullptr;
+  const bool fits = C / VEC <= AMD_TPB;  // one channel group per thread
+#define BAPPLY(MASK_, REGC_, POOL_, SMEM_, GS_)                             \
+  bn_bwd_apply_kernel<devT, VEC, MASK_, false, true, false, REGC_, POOL_>   \
+      <<<agrid, AMD_TPB, SMEM_, stream>>>(                                  \
+          x, go, gx, nullptr, k.A.data_ptr<float>(),                        \
+          k.Bc.data_ptr<float>(), k.Dc.data_ptr<float>(), scp, shp,         \
+          total_vec, (int)C, BNDualBwdSide<devT>{}, GS_)
+  if (pool != nullptr) {
+    TORCH_CHECK(affine && fits, "pool-gather bwd apply: unsupported form");
+    BAPPLY(2, true, true, 0, *pool);
+  } else if (bn_regcoef_enabled() && fits) {
+    if (affine) BAPPLY(2, true, false, 0, BNGradSrc<devT>{});
+    else BAPPLY(0, true, false, 0, BNGradSrc<devT>{});
+  } else {
+    const size_t smem = (affine ? 5 : 3) * C * sizeof(float);
+    if (affine) BAPPLY(2, false, false, smem, BNGradSrc<devT>{});
+    else BAPPLY(0, false, false, smem, BNGradSrc<devT>{});
+  }
+#undef BAPPLY
+  CHECK_CUDA_OK();
+}
+
 // the dual-BN tail is register-path only: same C on both sides and
 // C/VEC within one block (wide-C would need its own masked branch)
 static void check_dual(const at::Tensor& x3, const at::Tensor& x_d) {
@@ -731,34 +1025,11 @@ std::vector<at::Tensor> batch_norm_fwd_train(
   at::Tensor mask;
   if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
-  auto stream = at::cuda::getCurrentCUDAStream();
   auto st = bn_train_stats(x, std::nullopt, weight, bias, running_mean,
                            running_var, momentum, eps);
   auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
        &shift = st.shift;
-
-  dispatch_vec(x, [&](auto* tp, auto vec) {
-    using devT = std::remove_pointer_t<decltype(tp)>;
-    constexpr int VEC = decltype(vec)::value;
-    long total_vec = R * C / VEC;
-    int agrid = amd_grid(total_vec);
-    size_t smem = 2 * C * sizeof(float);
-    const devT* zp =
-        addend ? (const devT*)addend->const_data_ptr() : nullptr;
-#define APPLY(RELU_, ADD_)                                                  \
-  bn_apply_kernel<devT, VEC, RELU_, ADD_, true>                             \
-      <<<agrid, AMD_TPB, smem, stream>>>(                                   \
-          (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),         \
-          mask.defined() ? mask.data_ptr<unsigned char>() : nullptr,        \
-          scale.data_ptr<float>(), shift.data_ptr<float>(),     \
-          total_vec, (int)C)
-    if (relu && addend) APPLY(true, true);
-    else if (relu) APPLY(true, false);
-    else if (addend) APPLY(false, true);
-    else APPLY(false, false);
-#undef APPLY
-    CHECK_CUDA_OK();
-  });
+  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
   if (!mask.defined()) mask = at::empty({0}, x.options().dtype(at::kByte));
   return {y, mean, invstd, scale, shift, mask};
 }
@@ -776,33 +1047,11 @@ std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
   at::Tensor mask;
   if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
-  auto stream = at::cuda::getCurrentCUDAStream();
   auto st = bn_train_stats(x, parts, weight, bias, running_mean, running_var,
                            momentum, eps);
   auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
        &shift = st.shift;
-  dispatch_vec(x, [&](auto* tp, auto vec) {
-    using devT = std::remove_pointer_t<decltype(tp)>;
-    constexpr int VEC = decltype(vec)::value;
-    long total_vec = R * C / VEC;
-    int agrid = amd_grid(total_vec);
-    size_t smem = 2 * C * sizeof(float);
-    const devT* zp =
-        addend ? (const devT*)addend->const_data_ptr() : nullptr;
-#define APPLY2(RELU_, ADD_)                                                 \
-  bn_apply_kernel<devT, VEC, RELU_, ADD_, true>                             \
-      <<<agrid, AMD_TPB, smem, stream>>>(                                   \
-          (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),         \
-          mask.defined() ? mask.data_ptr<unsigned char>() : nullptr,        \
-          scale.data_ptr<float>(), shift.data_ptr<float>(),                 \
-          total_vec, (int)C)
-    if (relu && addend) APPLY2(true, true);
-    else if (relu) APPLY2(true, false);
-    else if (addend) APPLY2(false, true);
-    else APPLY2(false, false);
-#undef APPLY2
-    CHECK_CUDA_OK();
-  });
+  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
   if (!mask.defined()) mask = at::empty({0}, x.options().dtype(at::kByte));
   return {y, mean, invstd, scale, shift, mask};
 }
@@ -926,28 +1175,7 @@ at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
       running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
       scale.data_ptr<float>(), shift.data_ptr<float>(), (int)C, (float)eps);
   CHECK_CUDA_OK();
-  dispatch_vec(x, [&](auto* tp, auto vec) {
-    using devT = std::remove_pointer_t<decltype(tp)>;
-    constexpr int VEC = decltype(vec)::value;
-    long total_vec = R * C / VEC;
-    int agrid = amd_grid(total_vec);
-    size_t smem = 2 * C * sizeof(float);
-    const devT* zp =
-        addend ? (const devT*)addend->const_data_ptr() : nullptr;
-#define APPLY(RELU_, ADD_)                                                  \
-  bn_apply_kernel<devT, VEC, RELU_, ADD_, true>                             \
-      <<<agrid, AMD_TPB, smem, stream>>>(                                   \
-          (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),         \
-          mask.defined() ? mask.data_ptr<unsigned char>() : nullptr,        \
-          scale.data_ptr<float>(), shift.data_ptr<float>(),     \
-          total_vec, (int)C)
-    if (relu && addend) APPLY(true, true);
-    else if (relu) APPLY(true, false);
-    else if (addend) APPLY(false, true);
-    else APPLY(false, false);
-#undef APPLY
-    CHECK_CUDA_OK();
-  });
+  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
   return y;
 }
 
@@ -959,7 +1187,12 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> scale,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
-                                       std::optional<at::Tensor> relu_mask) {
+                                       std::optional<at::Tensor> relu_mask,
+                                       bool grad_out2_compact) {
+  // grad_out2_compact: grad_out2 is the [N*Hs*Ws, C] dgrad of a stride-2
+  // 1x1 conv (Hs = ceil(H/2), Ws = ceil(W/2)); the reduce reads it at the
+  // even positions and adds 0 elsewhere, which is the tensor
+  // scatter_rows_x2 would have written.  Register path only.
   // Pass structure (every kernel is an HBM-bound R x C stream, so passes
   // are the whole cost):
   //  * no relu:                reduce(x,go) -> apply(x,go -> gx)
@@ -986,6 +1219,23 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   at::Tensor ghat;
   if (mask_y || grad_out2) ghat = at::empty_like(grad_out);
   auto stream = at::cuda::getCurrentCUDAStream();
+  const long H = x.size(2), W = x.size(3);
+  const long Hs = (H + 1) / 2, Ws = (W + 1) / 2;
+  if (grad_out2_compact) {
+    TORCH_CHECK(grad_out2.has_value() && grad_out2->is_cuda() &&
+                    grad_out2->dim() == 2 && grad_out2->is_contiguous() &&
+                    grad_out2->scalar_type() == x.scalar_type() &&
+                    grad_out2->size(0) == x.size(0) * Hs * Ws &&
+                    grad_out2->size(1) == C,
+                "batch_norm_bwd: compact grad_out2 must be a contiguous "
+                "[N*ceil(H/2)*ceil(W/2), C] tensor of x's dtype");
+    TORCH_CHECK(C * (long)x.element_size() / 16 <= AMD_TPB,
+                "batch_norm_bwd: C too wide for a compact grad_out2: ", C);
+  } else if (grad_out2) {
+    check_nhwc(*grad_out2);
+    TORCH_CHECK(grad_out2->sizes() == x.sizes(),
+                "batch_norm_bwd: grad_out2 shape mismatch");
+  }
 
   dispatch_vec(x, [&](auto* tp, auto vec) {
     using devT = std::remove_pointer_t<decltype(tp)>;
@@ -994,25 +1244,32 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
     const float* shp = affine_mask ? shift->data_ptr<float>() : nullptr;
     const devT* go2p = grad_out2
         ? (const devT*)grad_out2->const_data_ptr() : nullptr;
-#define REDUCE(MASK_, WG_, GO2_)                                            \
-  bn_reduce_kernel<devT, VEC, true, MASK_, WG_, GO2_>                       \
+    BNGradSrc<devT> gs;
+    if (grad_out2_compact) {
+      gs.gy = go2p;
+      gs.H = (int)H, gs.W = (int)W, gs.Hs = (int)Hs, gs.Ws = (int)Ws;
+    }
+#define REDUCE_G(MASK_, WG_, GO2_, GSRC_)                                   \
+  bn_reduce_kernel<devT, VEC, true, MASK_, WG_, GO2_, false, GSRC_>         \
       <<<rgrid, AMD_TPB, 0, stream>>>(                                      \
           (const devT*)x.const_data_ptr(),                                  \
           (const devT*)grad_out.const_data_ptr(), go2p,                     \
           yp, mean.data_ptr<float>(),                                       \
           invstd.data_ptr<float>(), scp, shp,                               \
           WG_ ? (devT*)ghat.data_ptr() : nullptr,                           \
-          sums.data_ptr<float>(), R, (int)C)
+          sums.data_ptr<float>(), R, (int)C, BNDualSide<devT>{}, gs)
+#define REDUCE(MASK_, WG_, GO2_) REDUCE_G(MASK_, WG_, GO2_, GSRC_NONE)
 // MASK 3: the fwd bitmask rides in the y operand slot
-#define REDUCE3(GO2_)                                                       \
-  bn_reduce_kernel<devT, VEC, true, 3, true, GO2_>                          \
+#define REDUCE3_G(GO2_, GSRC_)                                              \
+  bn_reduce_kernel<devT, VEC, true, 3, true, GO2_, false, GSRC_>            \
       <<<rgrid, AMD_TPB, 0, stream>>>(                                      \
           (const devT*)x.const_data_ptr(),                                  \
           (const devT*)grad_out.const_data_ptr(), go2p,                     \
           (const devT*)mkp, mean.data_ptr<float>(),                         \
           invstd.data_ptr<float>(), scp, shp,                               \
           (devT*)ghat.data_ptr(),                                           \
-          sums.data_ptr<float>(), R, (int)C)
+          sums.data_ptr<float>(), R, (int)C, BNDualSide<devT>{}, gs)
+#define REDUCE3(GO2_) REDUCE3_G(GO2_, GSRC_NONE)
     const unsigned char* mkp = (relu_mask && relu_mask->numel())
         ? relu_mask->data_ptr<unsigned char>() : nullptr;
     // only the MASK 1 reduce dereferences y (the affine-mask and bitmask
@@ -1021,7 +1278,11 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                 "batch_norm_bwd: y is required to mask a relu+addend BN "
                 "that saved no relu_mask");
     const devT* yp = y ? (const devT*)y->const_data_ptr() : nullptr;
-    if (mask_y && mkp && go2p) REDUCE3(true);
+    if (grad_out2_compact) {
+      if (mask_y && mkp) REDUCE3_G(true, GSRC_COMPACT);
+      else if (mask_y) REDUCE_G(1, true, true, GSRC_COMPACT);
+      else REDUCE_G(0, true, true, GSRC_COMPACT);
+    } else if (mask_y && mkp && go2p) REDUCE3(true);
     else if (mask_y && mkp) REDUCE3(false);
     else if (mask_y && go2p) REDUCE(1, true, true);
     else if (mask_y) REDUCE(1, true, false);
@@ -1030,27 +1291,82 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
     else REDUCE(0, false, false);
 #undef REDUCE
 #undef REDUCE3
+#undef REDUCE_G
+#undef REDUCE3_G
     CHECK_CUDA_OK();
     k = bn_bwd_coeffs(sums, weight, mean, invstd, R, C);
-    long total_vec = R * C / VEC;
-    int agrid = amd_grid(total_vec);
-    size_t smem = (affine_mask ? 5 : 3) * C * sizeof(float);
     // use the materialized ghat whenever the reduce produced it (mask or
     // summed grad_out2); otherwise the raw grad_out
     const devT* go_in = ghat.defined()
                             ? (const devT*)ghat.const_data_ptr()
                             : (const devT*)grad_out.const_data_ptr();
-#define BAPPLY(MASK_)                                                       \
-  bn_bwd_apply_kernel<devT, VEC, MASK_, false, true>                        \
-      <<<agrid, AMD_TPB, smem, stream>>>(                                   \
-          (const devT*)x.const_data_ptr(), go_in, (devT*)gx.data_ptr(),     \
-          nullptr, k.A.data_ptr<float>(), k.Bc.data_ptr<float>(),           \
-          k.Dc.data_ptr<float>(), scp, shp, total_vec, (int)C)
-    if (affine_mask) BAPPLY(2);
-    else BAPPLY(0);
-#undef BAPPLY
-    CHECK_CUDA_OK();
+    bn_bwd_apply_launch<devT, VEC>((const devT*)x.const_data_ptr(), go_in,
+                                   (devT*)gx.data_ptr(), k, scp, shp, R, C,
+                                   nullptr);
   });
   if (!ghat.defined()) ghat = grad_out;  // placeholder (no addend path)
   return {gx, k.gw, k.gb, ghat};
+}
+
+// Stem BN backward with the max pool's backward folded in: grad_out of the
+// BN is never materialized — the reduce and the affine-mask apply gather
+// it from the pool-output gradient(s) and the argmax codes.  grad_pool2 is
+// the gradient from the pool output's second consumer (GradCell), summed
+// per window as T(gy + gy2).  Returns {gx, gw, gb}.
+std::vector<at::Tensor> batch_norm_bwd_pool(
+    at::Tensor x, at::Tensor grad_pool, std::optional<at::Tensor> grad_pool2,
+    at::Tensor idx, at::Tensor weight, at::Tensor mean, at::Tensor invstd,
+    at::Tensor scale, at::Tensor shift) {
+  check_nhwc(x);
+  check_nhwc(grad_pool);
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const long Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const long R = N * H * W;
+  const std::vector<int64_t> pool_shape{N, C, Ho, Wo};
+  TORCH_CHECK(grad_pool.sizes() == pool_shape &&
+                  grad_pool.scalar_type() == x.scalar_type(),
+              "batch_norm_bwd_pool: grad_pool must be [N,C,Ho,Wo] of x's "
+              "dtype");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == at::kByte &&
+                  idx.sizes() == pool_shape &&
+                  idx.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "batch_norm_bwd_pool: idx must be NHWC u8 [N,C,Ho,Wo]");
+  if (grad_pool2) {
+    check_nhwc(*grad_pool2);
+    TORCH_CHECK(grad_pool2->sizes() == pool_shape &&
+                    grad_pool2->scalar_type() == x.scalar_type(),
+                "batch_norm_bwd_pool: grad_pool2 shape/dtype mismatch");
+  }
+  TORCH_CHECK(C * (long)x.element_size() / 16 <= AMD_TPB,
+              "batch_norm_bwd_pool: C too wide for the register path: ", C);
+  TORCH_CHECK(R < (1L << 31), "batch_norm_bwd_pool: too many rows");
+  auto opts = x.options().dtype(at::kFloat);
+  const int rgrid = bn_reduce_grid(R, C);
+  auto sums = at::empty({rgrid, 2 * C}, opts);
+  BNBwdCoeffs k;
+  auto gx = at::empty_like(x);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  dispatch_vec(x, [&](auto* tp, auto vec) {
+    using devT = std::remove_pointer_t<decltype(tp)>;
+    constexpr int VEC = decltype(vec)::value;
+    const float* scp = scale.data_ptr<float>();
+    const float* shp = shift.data_ptr<float>();
+    BNGradSrc<devT> gs;
+    gs.gy = (const devT*)grad_pool.const_data_ptr();
+    gs.gy2 = grad_pool2 ? (const devT*)grad_pool2->const_data_ptr() : nullptr;
+    gs.idx = idx.data_ptr<unsigned char>();
+    gs.H = (int)H, gs.W = (int)W, gs.Hs = (int)Ho, gs.Ws = (int)Wo;
+    bn_reduce_kernel<devT, VEC, true, 2, false, false, false, GSRC_POOL>
+        <<<rgrid, AMD_TPB, 0, stream>>>(
+            (const devT*)x.const_data_ptr(), nullptr, nullptr, nullptr,
+            mean.data_ptr<float>(), invstd.data_ptr<float>(), scp, shp,
+            nullptr, sums.data_ptr<float>(), R, (int)C, BNDualSide<devT>{},
+            gs);
+    CHECK_CUDA_OK();
+    k = bn_bwd_coeffs(sums, weight, mean, invstd, R, C);
+    bn_bwd_apply_launch<devT, VEC>((const devT*)x.const_data_ptr(), nullptr,
+                                   (devT*)gx.data_ptr(), k, scp, shp, R, C,
+                                   &gs);
+  });
+  return {gx, k.gw, k.gb};
 }

@@ -64,7 +64,12 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> scale,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
-                                       std::optional<at::Tensor> relu_mask);
+                                       std::optional<at::Tensor> relu_mask,
+                                       bool grad_out2_compact);
+std::vector<at::Tensor> batch_norm_bwd_pool(
+    at::Tensor x, at::Tensor grad_pool, std::optional<at::Tensor> grad_pool2,
+    at::Tensor idx, at::Tensor weight, at::Tensor mean, at::Tensor invstd,
+    at::Tensor scale, at::Tensor shift);
 
 // gemm.hip
 at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
@@ -153,7 +158,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu"), py::arg("need_ghat"),
         py::arg("scale") = std::nullopt, py::arg("shift") = std::nullopt,
         py::arg("grad_out2") = std::nullopt,
-        py::arg("relu_mask") = std::nullopt);
+        py::arg("relu_mask") = std::nullopt,
+        py::arg("grad_out2_compact") = false);
+  m.def("batch_norm_bwd_pool", &batch_norm_bwd_pool, py::arg("x"),
+        py::arg("grad_pool"), py::arg("grad_pool2"), py::arg("idx"),
+        py::arg("weight"), py::arg("mean"), py::arg("invstd"),
+        py::arg("scale"), py::arg("shift"));
   m.def("gemm_bt", &gemm_bt, py::arg("A"), py::arg("B"),
         py::arg("f32_out") = false, py::arg("addend") = std::nullopt,
         py::arg("bias") = std::nullopt);

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from ._ext import require_ext, use_ext_for
-from .conv import GradCell
+from .conv import GradCell, _dsgrad_compact_enabled
 
 __all__ = ["batch_norm", "bn_add_relu", "bn_add_relu_downsample",
            "bn_relu_max_pool", "max_pool_3x3_s2", "global_avg_pool"]
@@ -61,15 +61,21 @@ class _BNFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, y, weight, mean, invstd, scale, shift, mask = ctx.saved_tensors
         e = require_ext()
-        go2 = None
+        go2, compact = None, False
         cell = getattr(ctx, "res_cell", None)
         if cell is not None and cell.g is not None:
-            go2 = cell.g.contiguous(memory_format=torch.channels_last)
+            if cell.meta is not None:
+                # compact [N*ho*wo, C] dgrad of the next block's stride-2
+                # downsample conv: the reduce reads it at the even positions
+                go2, compact = cell.g.contiguous(), True
+            else:
+                go2 = cell.g.contiguous(memory_format=torch.channels_last)
             cell.g = None
+            cell.meta = None
         grad_x, grad_w, grad_b, ghat = e.batch_norm_bwd(
             x, grad_out.contiguous(memory_format=torch.channels_last),
             y, weight, mean, invstd, ctx.relu, ctx.has_addend,
-            scale, shift, go2, mask)
+            scale, shift, go2, mask, compact)
         grad_addend = ghat if ctx.has_addend else None
         return (grad_x, grad_w, grad_b, None, None, None, None, None,
                 grad_addend, None, None)
@@ -105,6 +111,11 @@ def batch_norm(x: torch.Tensor, bn, relu: bool = False,
             # block-tail BNs publish a mailbox the NEXT residual block can
             # reroute its shortcut gradient into (ResidualGradTap)
             cell = GradCell() if (relu and ac is not None) else None
+            if cell is not None:
+                # this backward's reduce also takes the next block's
+                # stride-2 downsample dgrad in compact form
+                cell.compact_ok = (_dsgrad_compact_enabled()
+                                   and _vec_ok(xc, 256))
             out = _BNFunction.apply(xc, bn.weight, bn.bias, bn.running_mean,
                                     bn.running_var, bn.momentum, bn.eps,
                                     relu, ac, parts, cell)
@@ -174,6 +185,12 @@ def _stemfuse_enabled() -> bool:
     return os.environ.get("AMDTRAIN_STEMFUSE", "1") == "1"
 
 
+def _poolbwd_fuse_enabled() -> bool:
+    """AMDTRAIN_POOLBWD_FUSE=0 restores the separate stem pool backward
+    (and the eager add of the pool output's two gradients)."""
+    return os.environ.get("AMDTRAIN_POOLBWD_FUSE", "1") == "1"
+
+
 def _vec_ok(x: torch.Tensor, max_groups: int) -> bool:
     """The kernels' channel guards: pow2 C, whole 16-byte packs, and at most
     ``max_groups`` packs per row."""
@@ -240,31 +257,46 @@ def max_pool_3x3_s2(x: torch.Tensor) -> torch.Tensor:
 class _BNReLUMaxPool(torch.autograd.Function):
     """Stem: max_pool_3x3_s2(relu(bn(x))) with BN+ReLU applied per tap inside
     the pool kernel, so the 112x112x64 activation is neither written nor
-    saved.  Backward is the pool gather followed by the BN backward in its
-    affine-mask form, which recomputes the ReLU mask from scale/shift."""
+    saved.  Backward is the BN backward in its affine-mask form, which
+    recomputes the ReLU mask from scale/shift, with the pool's backward
+    gather folded into its two kernels (``res_cell`` given): the
+    112x112x64 gradient is never written either, and the gradient of the
+    pool output's second consumer arrives through the cell instead of an
+    eager add.  Without a cell: pool backward, then BN backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
-                eps, parts):
+                eps, parts, res_cell=None):
         e = require_ext()
         mean, invstd, scale, shift = e.batch_norm_train_stats(
             x, parts, weight, bias, running_mean, running_var,
             float(momentum), float(eps))
         y, idx = e.max_pool_3x3_s2_fwd(x, scale, shift)
         ctx.save_for_backward(x, idx, weight, mean, invstd, scale, shift)
+        ctx.res_cell = res_cell
         return y
 
     @staticmethod
     def backward(ctx, grad_out):
         x, idx, weight, mean, invstd, scale, shift = ctx.saved_tensors
         e = require_ext()
-        gp = e.max_pool_3x3_s2_bwd(
-            grad_out.contiguous(memory_format=torch.channels_last), idx,
-            int(x.size(2)), int(x.size(3)))
-        grad_x, grad_w, grad_b, _ = e.batch_norm_bwd(
-            x, gp, None, weight, mean, invstd, True, False, scale, shift,
-            None, None)
-        return grad_x, grad_w, grad_b, None, None, None, None, None
+        go = grad_out.contiguous(memory_format=torch.channels_last)
+        cell = getattr(ctx, "res_cell", None)
+        if cell is not None:
+            go2 = None
+            if cell.g is not None:
+                go2 = cell.g.to(go.dtype).contiguous(
+                    memory_format=torch.channels_last)
+                cell.g = None
+            grad_x, grad_w, grad_b = e.batch_norm_bwd_pool(
+                x, go, go2, idx, weight, mean, invstd, scale, shift)
+        else:
+            gp = e.max_pool_3x3_s2_bwd(go, idx, int(x.size(2)),
+                                       int(x.size(3)))
+            grad_x, grad_w, grad_b, _ = e.batch_norm_bwd(
+                x, gp, None, weight, mean, invstd, True, False, scale,
+                shift, None, None)
+        return grad_x, grad_w, grad_b, None, None, None, None, None, None
 
 
 def bn_relu_max_pool(x: torch.Tensor, bn) -> torch.Tensor:
@@ -276,10 +308,18 @@ def bn_relu_max_pool(x: torch.Tensor, bn) -> torch.Tensor:
         if bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
         parts = getattr(x, "_amdtrain_bn_stats", None)
-        return _BNReLUMaxPool.apply(
+        # the pool-gather backward is register-path only (C/VEC <= 256); it
+        # also publishes the mailbox the first block's ResidualGradTap
+        # reroutes the pool output's second gradient into
+        cell = GradCell() if (_poolbwd_fuse_enabled()
+                              and _vec_ok(x, 256)) else None
+        out = _BNReLUMaxPool.apply(
             x.contiguous(memory_format=torch.channels_last), bn.weight,
             bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
-            parts)
+            parts, cell)
+        if cell is not None:
+            out._amdtrain_next_cell = cell
+        return out
     return max_pool_3x3_s2(batch_norm(x, bn, relu=True))
 
 
