@@ -31,6 +31,35 @@ def _fuse_stats_enabled() -> bool:
     return os.environ.get("AMDTRAIN_FUSE_BNSTATS", "1") == "1"
 
 
+def _stem_s2d_enabled() -> bool:
+    """Width space-to-depth form of the thin-channel 7x7 s2 stem (see
+    stem_s2d_input): AMDTRAIN_STEM_S2D=1.  Off by default although it is
+    the faster form (profiles/README.md): its K grouping and its
+    statistics epilogue change the last bits of the stem output, and a
+    training run amplifies those, so results would no longer repeat the
+    49-tap path's.  The default keeps the 3->8 channel-padded 49 taps."""
+    return os.environ.get("AMDTRAIN_STEM_S2D", "0") == "1"
+
+
+def _stem_nt64_enabled() -> bool:
+    """64-wide n-tile for the channel-padded 49-tap stem forward when
+    Cout <= 64 (same K order, identical output); AMDTRAIN_STEM_NT64=0 keeps
+    the 128-wide tile."""
+    return os.environ.get("AMDTRAIN_STEM_NT64", "1") == "1"
+
+
+def _s2parity_enabled() -> bool:
+    """Parity-class tiles for the stride-2 conv3x3 dgrad (conv3x3.hip);
+    AMDTRAIN_CONV3X3_S2PARITY=0 walks all 9 taps for every tile."""
+    return os.environ.get("AMDTRAIN_CONV3X3_S2PARITY", "1") == "1"
+
+
+def _nt64_enabled() -> bool:
+    """64-wide n-tile for conv3x3 outputs of <= 64 channels;
+    AMDTRAIN_CONV3X3_NT64=0 keeps the 128-wide tile."""
+    return os.environ.get("AMDTRAIN_CONV3X3_NT64", "1") == "1"
+
+
 def _wgrad2_enabled() -> bool:
     """tn2_wgrad (wgrad.hip): tr-read TN core — single launch for all 9
     conv3x3 taps, no atomics, bitwise deterministic.  Default on;
@@ -208,10 +237,12 @@ class _Conv3x3(torch.autograd.Function):
         # channels_last weight [Cout,Cin,3,3] is [Cout][kh][kw][Cin] in memory
         w2d = weight.contiguous(memory_format=torch.channels_last) \
             .permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+        nt64 = _nt64_enabled()
         if _fuse_stats_enabled():
-            y2d, stats = e.conv3x3_fwd_stats(x2d, n, h, w, stride, w2d)
+            y2d, stats = e.conv3x3_fwd_stats(x2d, n, h, w, stride, w2d,
+                                             False, nt64)
         else:
-            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d)
+            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, nt64)
             stats = torch.empty(0, device=x.device)
         ctx.save_for_backward(x2d, w2d)
         ctx.meta = (n, cin, h, w, stride, cout)
@@ -229,7 +260,8 @@ class _Conv3x3(torch.autograd.Function):
         n, cin, h, w, stride, cout = ctx.meta
         gy = grad_y.contiguous(memory_format=torch.channels_last)
         gy2d = _rows(gy).to(torch.bfloat16)
-        dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d)
+        dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, False,
+                               _s2parity_enabled(), _nt64_enabled())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         # [Cout, 9*Cin] f32 — single-launch tap-gather TN (wgrad.hip)
         dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2) \
@@ -287,9 +319,9 @@ class _ConvGrouped3x3(torch.autograd.Function):
         banded = (cin == cout and cin % 128 == 0)
         if _fuse_stats_enabled():
             y2d, stats = e.conv3x3_fwd_stats(x2d, n, h, w, stride, w2d,
-                                             banded)
+                                             banded, _nt64_enabled())
         else:
-            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d)
+            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, _nt64_enabled())
             stats = torch.empty(0, device=x.device)
         ctx.save_for_backward(x2d, w2d)
         ctx.meta = (n, cin, h, w, stride, cout, groups, banded)
@@ -309,7 +341,8 @@ class _ConvGrouped3x3(torch.autograd.Function):
         sout = cout // groups
         gy = grad_y.contiguous(memory_format=torch.channels_last)
         gy2d = _rows(gy).to(torch.bfloat16)
-        dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, banded)
+        dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, banded,
+                               _s2parity_enabled(), _nt64_enabled())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         if banded and _wgrad2_enabled():
             # compact band [Cout, 9, 128]: extract the group diagonal of
@@ -342,20 +375,82 @@ def conv3x3_grouped_mfma(x: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+def stem_s2d_input(x_nhwc: torch.Tensor) -> torch.Tensor:
+    """[N, H, W, C] (C <= 4, W even) -> X' [N, H, W/2, 8]: channels padded
+    to 4, then two neighbouring pixels share one 8-channel row, channel
+    index p*4 + c for pixel 2*group + p.  After the pad this is a pure
+    reinterpretation of the NHWC memory — no second copy."""
+    n, h, w, c = x_nhwc.shape
+    assert c <= 4 and w % 2 == 0
+    x4 = torch.nn.functional.pad(x_nhwc, (0, 4 - c))
+    return x4.reshape(n, h, w // 2, 8)
+
+
+def stem_s2d_weight(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, C, 7, 7] -> W2' [Cout, kh=7, g=4, p=2, c=4] with
+    W2'[cout, kh, g, p, c] = w[cout, c, kh, 2g+p-1], zero where kw = -1 or
+    c >= C.
+
+    With X' = stem_s2d_input(x), the 7x7 stride-2 pad-3 conv of x equals
+    the conv of X' with a 7 x 4 (kh x g) kernel over 8 channels, stride
+    (2, 1), top padding 3 and left padding 2 groups, at the original
+    Hout x Wout: input pixel 2*wo - 3 + kw is group wo - 2 + g, slot p.
+    The image edges sit at even pixels, so padding comes in whole groups;
+    the one zero-weight slot (g = 0, p = 0) reads real data."""
+    cout, c, kh, kw = weight.shape
+    assert c <= 4 and kh == 7 and kw == 7
+    wp = torch.nn.functional.pad(weight, (1, 0, 0, 0, 0, 4 - c))
+    return wp.permute(0, 2, 3, 1).reshape(cout, 7, 4, 2, 4)
+
+
+def stem_s2d_dweight(dw2: torch.Tensor, cin: int) -> torch.Tensor:
+    """Inverse index gather of stem_s2d_weight: dW2' [Cout, 224] (or any
+    shape of 7*4*2*4 trailing elements) -> dW [Cout, cin, 7, 7]."""
+    cout = dw2.shape[0]
+    return dw2.reshape(cout, 7, 8, 4)[:, :, 1:, :cin].permute(0, 3, 1, 2)
+
+
+def _stem_s2d_ok(weight: torch.Tensor, w: int, stride: int, pad: int) -> bool:
+    return (weight.shape[1] <= 4 and tuple(weight.shape[2:]) == (7, 7)
+            and stride == 2 and pad == 3 and w % 2 == 0)
+
+
 class _ConvGeneric(torch.autograd.Function):
     """Generic implicit-GEMM conv (element-gather im2col) — serves the 7x7
     stem and any other odd configuration.  Input gradient gathers dY
-    through the transposed-conv map (conv_generic_dgrad) when needed."""
+    through the transposed-conv map (conv_generic_dgrad) when needed.
+
+    ``s2d`` runs a thin-channel 7x7 s2 p3 conv in its width space-to-depth
+    form (stem_s2d_weight): K = 224 instead of 416, and the forward also
+    emits the BN-statistics partials (second, non-differentiable output;
+    empty otherwise)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
-                pad: int):
+                pad: int, s2d: bool = False, nt64: bool = False):
         e = require_ext()
         n, cin, h, w = x.shape
         cout, _, kh, kw = weight.shape
         xc = x.contiguous(memory_format=torch.channels_last)
         x2d = _rows(xc)
+        ho = (h + 2 * pad - kh) // stride + 1
+        wo = (w + 2 * pad - kw) // stride + 1
+        ctx.s2d = s2d
+        if s2d:
+            x8 = stem_s2d_input(x2d.view(n, h, w, cin)) \
+                .view(n * h * (w // 2), 8)
+            w2 = stem_s2d_weight(weight).reshape(cout, 224)
+            geom = (n, h, w // 2, 7, 4, 2, 3, w2, 1, 2, ho, wo, True)
+            if _fuse_stats_enabled():
+                y2d, stats = e.conv_generic_fwd_stats(x8, *geom)
+            else:
+                y2d = e.conv_generic_fwd(x8, *geom)
+                stats = torch.empty(0, device=x.device)
+            ctx.save_for_backward(x8, weight)
+            ctx.meta = (n, cin, h, w, kh, kw, stride, pad, cout, 224, 8)
+            ctx.mark_non_differentiable(stats)
+            return y2d.view(n, ho, wo, cout).permute(0, 3, 1, 2), stats
         w4 = weight.contiguous(memory_format=torch.channels_last) \
             .permute(0, 2, 3, 1)                       # [Cout, KH, KW, Cin]
         if cin < 8:
@@ -371,16 +466,17 @@ class _ConvGeneric(torch.autograd.Function):
         w2 = w4.reshape(cout, k)
         if kpad != k:
             w2 = torch.nn.functional.pad(w2, (0, kpad - k))
-        y2d = e.conv_generic_fwd(x2d, n, h, w, kh, kw, stride, pad, w2)
+        y2d = e.conv_generic_fwd(x2d, n, h, w, kh, kw, stride, pad, w2,
+                                 0, -1, 0, 0, nt64)
         ctx.save_for_backward(x2d, weight)
         ctx.meta = (n, cin, h, w, kh, kw, stride, pad, cout, k, cin_k)
-        ho = (h + 2 * pad - kh) // stride + 1
-        wo = (w + 2 * pad - kw) // stride + 1
-        return y2d.view(n, ho, wo, cout).permute(0, 3, 1, 2)
+        stats = torch.empty(0, device=x.device)
+        ctx.mark_non_differentiable(stats)
+        return y2d.view(n, ho, wo, cout).permute(0, 3, 1, 2), stats
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, grad_y: torch.Tensor):
+    def backward(ctx, grad_y: torch.Tensor, _grad_stats=None):
         e = require_ext()
         x2d, weight = ctx.saved_tensors
         n, cin, h, w, kh, kw, stride, pad, cout, k, cin_k = ctx.meta
@@ -398,7 +494,16 @@ class _ConvGeneric(torch.autograd.Function):
             dx2d = e.conv_generic_dgrad(gy2d, w2p.contiguous(), n, h, w,
                                         kh, kw, stride, pad)
             dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        if _wgrad2_enabled() and cout % 8 == 0:
+        if ctx.s2d:
+            # x2d is X' [N*H*(W/2), 8]: 28 taps of 8 channels, so K' = 224
+            # sits in one k-tile and dY is staged once
+            ho = (h + 2 * pad - kh) // stride + 1
+            wo = (w + 2 * pad - kw) // stride + 1
+            dwp = e.tn2_wgrad(gy2d, x2d, 28, n, h, w // 2, 2, 2, 7, 4, 3,
+                              1, 2, ho, wo)              # [Cout, 224] f32
+            dw = stem_s2d_dweight(dwp, cin) \
+                .contiguous(memory_format=torch.channels_last)
+        elif _wgrad2_enabled() and cout % 8 == 0:
             # tap-gather TN core; x2d is already channel-padded (fwd)
             dwp = e.tn2_wgrad(gy2d, x2d, kh * kw, n, h, w, stride, 2,
                               kh, kw, pad)               # [Cout, taps*cin_k]
@@ -411,12 +516,19 @@ class _ConvGeneric(torch.autograd.Function):
             dw = dw2[:, :k].view(cout, kh * kw, cin_k)[:, :, :cin] \
                 .reshape(cout, kh, kw, cin).permute(0, 3, 1, 2) \
                 .contiguous(memory_format=torch.channels_last)
-        return dx, dw, None, None
+        return dx, dw, None, None, None, None
 
 
 def conv_stem_mfma(x: torch.Tensor, weight: torch.Tensor, stride: int,
                    pad: int) -> torch.Tensor:
-    return _ConvGeneric.apply(x, weight, stride, pad)
+    # the s2d weight gradient exists in the tap-gather TN core only
+    s2d = (_stem_s2d_enabled() and _wgrad2_enabled()
+           and _stem_s2d_ok(weight, x.shape[3], stride, pad))
+    y, stats = _ConvGeneric.apply(x, weight, stride, pad, s2d,
+                                  _stem_nt64_enabled())
+    if stats.numel():
+        y._amdtrain_bn_stats = stats
+    return y
 
 
 def _conv1x1_env_default() -> str:

@@ -86,6 +86,63 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
+// ---- implicit-GEMM conv epilogue: BN-statistics partials --------------------
+// (shared by conv3x3.hip and conv_stem.hip)
+// per-block column (sum, sumsq) of the fp32 accumulator tile (see
+// gemm.hip) of a 128-row block whose 4 waves form a 2m x 2n grid of
+// 4 x (NTE/32) 16x16 fragments; NTE = n-tile width (128 or 64).  Writes row
+// bm of stats [nbm][2*N]; lds_scratch needs 4*NTE floats.
+template <int NTE = 128>
+__device__ __forceinline__ void conv_epilogue_stats(
+    float* __restrict__ stats, const float* acc_flat, long m0, long M,
+    long n0, long N, int bm, int wm, int wn, int fr, int fq,
+    void* lds_scratch) {
+  constexpr int NF = NTE / 32;  // n fragments per wave
+  float* srow = stats + (long)bm * 2 * N;
+  float s1[NF], s2[NF];
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    s1[j] = 0.f;
+    s2[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        long row = m0 + wm + i * 16 + fq * 4 + r;
+        float v = (row < M) ? acc_flat[(i * NF + j) * 4 + r] : 0.f;
+        s1[j] += v;
+        s2[j] += v * v;
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+#pragma unroll
+    for (int off = 32; off >= 16; off >>= 1) {
+      s1[j] += __shfl_down(s1[j], off, AMD_WAVE);
+      s2[j] += __shfl_down(s2[j], off, AMD_WAVE);
+    }
+  }
+  float* red = (float*)lds_scratch;
+  __syncthreads();
+  if (fq == 0) {
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      int col = wn + j * 16 + fr;
+      red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 0] = s1[j];
+      red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 1] = s2[j];
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  for (int col = t; col < NTE; col += AMD_TPB) {
+    long n = n0 + col;
+    if (n < N) {
+      srow[n] = red[col * 2] + red[2 * NTE + col * 2];
+      srow[N + n] = red[col * 2 + 1] + red[2 * NTE + col * 2 + 1];
+    }
+  }
+}
+
 // ---- multi-tensor-apply metadata (apex amp_C style, struct by value) -------
 
 constexpr int MT_TENSORS = 24;

@@ -13,6 +13,12 @@
 // mfma_f32_16x16x32_bf16 fragments, global_load_lds staging).  Padding is
 // handled with a 16 B zero page: out-of-bounds gather rows load from it, so
 // no LDS pre-zeroing pass and no boundary branches in the MFMA loop.
+//
+// Two variants avoid MFMA work on operands that are zero by construction:
+// outputs of <= 64 channels run a 64-wide n-tile (NT = 64), and the
+// stride-2 dgrad tiles each (h&1, w&1) parity class on its own and walks
+// only that class's taps (PAR).  Both reproduce the 128-wide all-taps
+// loop value for value.
 #include "common.h"
 
 namespace {
@@ -73,11 +79,21 @@ struct UnitCoord {
   int hb, wb;  // tap-0 pixel coords (may be negative / out of range)
 };
 
-template <bool DGRAD>
-__device__ __forceinline__ UnitCoord decode_unit(long m, const ConvGeom& g) {
+// PAR (stride-2 dgrad, even H and W): m is a row of parity class
+// cls = (h&1)*2 + (w&1), ordered (n, h>>1, w>>1) within the class
+template <bool DGRAD, bool PAR = false>
+__device__ __forceinline__ UnitCoord decode_unit(long m, const ConvGeom& g,
+                                                 int cls = 0) {
   UnitCoord u;
   long t = m;
-  if (DGRAD) {  // m ranges over INPUT pixels; gather reads dY [Hout,Wout]
+  if (PAR) {
+    const int W2 = g.W >> 1, H2 = g.H >> 1;
+    const int w2 = (int)(t % W2); t /= W2;
+    const int h2 = (int)(t % H2); t /= H2;
+    u.n_off = t * (long)g.Hout * g.Wout;
+    u.hb = 2 * h2 + (cls >> 1) + 1;
+    u.wb = 2 * w2 + (cls & 1) + 1;
+  } else if (DGRAD) {  // m ranges over INPUT pixels; gather reads dY [Hout,Wout]
     const int w = (int)(t % g.W); t /= g.W;
     const int h = (int)(t % g.H); t /= g.H;
     u.n_off = t * (long)g.Hout * g.Wout;
@@ -93,12 +109,15 @@ __device__ __forceinline__ UnitCoord decode_unit(long m, const ConvGeom& g) {
   return u;
 }
 
-template <bool DGRAD>
+template <bool DGRAD, bool PAR = false>
 __device__ __forceinline__ long unit_row(const UnitCoord& u, int kh, int kw,
                                          const ConvGeom& g) {
   if (DGRAD) {
     int ho2 = u.hb - kh, wo2 = u.wb - kw;
-    if (g.stride == 2) {
+    if (PAR) {  // the block only walks taps of its class's parity
+      ho2 >>= 1;
+      wo2 >>= 1;
+    } else if (g.stride == 2) {
       if ((ho2 | wo2) & 1) return -1;
       ho2 >>= 1;
       wo2 >>= 1;
@@ -112,7 +131,7 @@ __device__ __forceinline__ long unit_row(const UnitCoord& u, int kh, int kw,
 }
 
 // BKT = K-step depth (32 or 64): BKT/8 16-B units per m-row, BKT/16 rounds
-template <bool DGRAD, int BKT>
+template <bool DGRAD, int BKT, bool PAR = false>
 __device__ __forceinline__ void stage_gathered(
     const bf16* __restrict__ src, int ld, const UnitCoord* uc, int c0, int kh,
     int kw, const ConvGeom& g, const bf16* __restrict__ zero_page,
@@ -122,7 +141,7 @@ __device__ __forceinline__ void stage_gathered(
 #pragma unroll
   for (int rnd = 0; rnd < BKT / 16; ++rnd) {
     int unit = rnd * GEMM_TPB + t;
-    long row = unit_row<DGRAD>(uc[rnd], kh, kw, g);
+    long row = unit_row<DGRAD, PAR>(uc[rnd], kh, kw, g);
     const bf16* p = row < 0 ? zero_page
                             : src + row * (long)ld + c0 +
                                   (unit % UPR) * 8;
@@ -175,59 +194,6 @@ __device__ __forceinline__ void stage_plain(
   }
 }
 
-// per-block column (sum, sumsq) of the fp32 accumulator tile (see
-// gemm.hip); NTE = n-tile width (128, or 64 for the banded variant)
-template <int NTE = 128>
-__device__ __forceinline__ void conv_epilogue_stats(
-    float* __restrict__ stats, const float* acc_flat, long m0, long M,
-    long n0, long N, int bm, int wm, int wn, int fr, int fq,
-    bf16* lds_scratch) {
-  constexpr int NF = NTE / 32;  // n fragments per wave
-  float* srow = stats + (long)bm * 2 * N;
-  float s1[NF], s2[NF];
-#pragma unroll
-  for (int j = 0; j < NF; ++j) {
-    s1[j] = 0.f;
-    s2[j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long row = m0 + wm + i * 16 + fq * 4 + r;
-        float v = (row < M) ? acc_flat[(i * NF + j) * 4 + r] : 0.f;
-        s1[j] += v;
-        s2[j] += v * v;
-      }
-  }
-#pragma unroll
-  for (int j = 0; j < NF; ++j) {
-#pragma unroll
-    for (int off = 32; off >= 16; off >>= 1) {
-      s1[j] += __shfl_down(s1[j], off, AMD_WAVE);
-      s2[j] += __shfl_down(s2[j], off, AMD_WAVE);
-    }
-  }
-  float* red = (float*)lds_scratch;
-  __syncthreads();
-  if (fq == 0) {
-#pragma unroll
-    for (int j = 0; j < NF; ++j) {
-      int col = wn + j * 16 + fr;
-      red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 0] = s1[j];
-      red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 1] = s2[j];
-    }
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  for (int col = t; col < NTE; col += GEMM_TPB) {
-    long n = n0 + col;
-    if (n < N) {
-      srow[n] = red[col * 2] + red[2 * NTE + col * 2];
-      srow[N + n] = red[col * 2 + 1] + red[2 * NTE + col * 2 + 1];
-    }
-  }
-}
-
 // fwd / dgrad main kernel.  DGRAD only changes the gather map; operand roles:
 //   fwd:   A = x rows (AC channels), B = w [NC, 9*AC], C = y [M, NC]
 //   dgrad: A = dy rows (AC = Cout), B = w' [NC = Cin, 9*Cout], C = dx
@@ -241,20 +207,33 @@ __device__ __forceinline__ void conv_epilogue_stats(
 // tiles while the MFMAs consume iteration it's (one barrier per iteration
 // instead of two; the barrier's implicit vmcnt(0) drains the DMA queue),
 // mirroring the gemm.hip DB loop.
+// PAR (stride-2 dgrad, even H and W): the M rows are ordered class-major
+// over the four (h&1, w&1) parity classes and each class is tiled on its
+// own, so a block's class is uniform and it walks only the taps whose
+// parity reaches its pixels — kh = 1 for even h, {0, 2} for odd h, same
+// for kw: 1, 2, 2 or 4 taps instead of 9, the other taps are all-zero
+// gathers.  Taps stay in ascending order with the same ks order inside,
+// so every output accumulates exactly the nonzero terms of the all-taps
+// loop in the same order.  M is the TOTAL row count (4 classes of M/4),
+// nbm = 4 * tiles-per-class; the class is the fastest block index so the
+// 1/2/2/4-tap blocks interleave evenly over the XCDs.
 template <bool DGRAD, int BKT = BK, bool BAND = false, int NT = 128,
-          bool DB = false>
+          bool DB = false, bool PAR = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
                bf16* __restrict__ C, long M, int AC, int NC, ConvGeom g,
                int nbm, int nbn, const bf16* __restrict__ zero_page,
                float* __restrict__ stats) {
-  __shared__ bf16 SMEM[(DB ? 2 : 1) * 2 * 128 * BKT];
+  static_assert(!PAR || (DGRAD && !BAND), "PAR is a dense-dgrad variant");
+  constexpr int STG = (128 + NT) * BKT;  // one A+B stage
+  __shared__ bf16 SMEM[(DB ? 2 : 1) * STG];
   bf16* const As = SMEM;
-  bf16* const Bs = SMEM + 128 * BKT;
 
   const int bid = xcd_swz(blockIdx.x, nbm * nbn);
   const int bm = bid / nbn, bn = bid % nbn;
-  const long m0 = (long)bm * 128, n0 = (long)bn * NT;
+  const int cls = PAR ? (bm & 3) : 0;  // (h&1)*2 + (w&1)
+  const long Mr = PAR ? (M >> 2) : M;  // rows in this block's tile space
+  const long m0 = (long)(PAR ? (bm >> 2) : bm) * 128, n0 = (long)bn * NT;
   constexpr int NFR = NT / 32;  // n fragments per wave (4 at NT=128)
 
   const int t = threadIdx.x;
@@ -273,18 +252,26 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
 #pragma unroll
   for (int rnd = 0; rnd < BKT / 16; ++rnd) {
     long m = m0 + (rnd * GEMM_TPB + t) / (BKT / 8);
-    if (m >= M) m = M - 1;
-    uc[rnd] = decode_unit<DGRAD>(m, g);
+    if (m >= Mr) m = Mr - 1;
+    uc[rnd] = decode_unit<DGRAD, PAR>(m, g, cls);
   }
 
   const int ks_lo = BAND ? (int)(n0 / BKT) : 0;
   const int ks_hi = BAND ? ks_lo + NT / BKT : AC / BKT;
   const int nks = ks_hi - ks_lo;
-  const int total = 9 * nks;
+  // PAR: odd rows/cols take taps {0, 2}, even ones tap {1}
+  const int par_h = cls >> 1, par_w = cls & 1;
+  const int total = (PAR ? (1 + par_h) * (1 + par_w) : 9) * nks;
   auto stage_it = [&](int it, bf16* as) {
-    const int tap = it / nks, ks = ks_lo + it % nks;
+    int tap = it / nks;
+    const int ks = ks_lo + it % nks;
+    if (PAR) {  // tap index within the class -> (kh, kw), ascending
+      const int khi = par_w ? (tap >> 1) : tap, kwi = par_w ? (tap & 1) : 0;
+      tap = (par_h ? 2 * khi : 1) * 3 + (par_w ? 2 * kwi : 1);
+    }
     const int kh = tap / 3, kw = tap % 3, c0 = ks * BKT;
-    stage_gathered<DGRAD, BKT>(A, AC, uc, c0, kh, kw, g, zero_page, as);
+    stage_gathered<DGRAD, BKT, PAR>(A, AC, uc, c0, kh, kw, g, zero_page,
+                                    as);
     if (NT == 128)
       stage_plain<BKT>(Bw, (long)9 * AC, n0, NC, (long)tap * AC + c0,
                        as + 128 * BKT);
@@ -314,7 +301,7 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     }
   };
   if (DB) {
-    constexpr int HB = 2 * 128 * BKT;
+    constexpr int HB = STG;
     if (total > 0) stage_it(0, SMEM);
     for (int it = 0; it < total; ++it) {
       bf16* const as = SMEM + (it & 1) * HB;
@@ -332,6 +319,38 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     }
   }
 
+  if (PAR) {
+    // class row -> true input row; one decode per 4-row fragment group,
+    // then step (w2, h2, n) with carries (host guarantees M < 2^31)
+    const unsigned W2 = g.W >> 1, H2 = g.H >> 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const unsigned mr = (unsigned)m0 + wm + i * 16 + fq * 4;
+      unsigned w2 = mr % W2, t2 = mr / W2;
+      unsigned h2 = t2 % H2, n = t2 / H2;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if ((long)mr + r < Mr) {
+          const long row = ((long)n * g.H + 2 * h2 + par_h) * g.W +
+                           2 * w2 + par_w;
+#pragma unroll
+          for (int j = 0; j < NFR; ++j) {
+            long col = n0 + wn + j * 16 + fr;
+            if (col < NC)
+              C[row * NC + col] = __float2bfloat16(acc[i][j][r]);
+          }
+        }
+        if (++w2 == W2) {
+          w2 = 0;
+          if (++h2 == H2) {
+            h2 = 0;
+            ++n;
+          }
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -491,7 +510,8 @@ std::vector<at::Tensor> conv3x3_fwd_stats_impl(at::Tensor x2d, long Nn,
                                                 long H, long W, long stride,
                                                 at::Tensor w2d,
                                                 bool want_stats,
-                                                bool banded = false) {
+                                                bool banded = false,
+                                                bool nt64 = true) {
   // x2d: [Nn*H*W, Cin] bf16 NHWC rows; w2d: [Cout, 9*Cin]
   TORCH_CHECK(x2d.is_cuda() && x2d.scalar_type() == at::kBFloat16);
   long Cin = x2d.size(1), Cout = w2d.size(0);
@@ -534,6 +554,17 @@ std::vector<at::Tensor> conv3x3_fwd_stats_impl(at::Tensor x2d, long Nn,
               (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
               (int)Cin, (int)Cout, g, nbm, nbn64,
               (const bf16*)zp.const_data_ptr(), stats_ptr);
+  } else if (nt64 && Cout <= 64 && conv3x3_db_enabled()) {
+    // narrow output (layer 1): the 64-wide n-tile issues no MFMAs on the
+    // clamped B rows 64..127 of the 128-wide tile; per-element K order
+    // and per-block row sets are unchanged, so y and the stats partials
+    // equal the 128-wide tile's
+    conv3x3_kernel<false, BK, false, 64, true>
+        <<<nbm, GEMM_TPB, 0, stream>>>(
+            (const bf16*)x2d.const_data_ptr(),
+            (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
+            (int)Cin, (int)Cout, g, nbm, 1,
+            (const bf16*)zp.const_data_ptr(), stats_ptr);
   } else if (bk64 && Cin % 64 == 0 && Cin >= 128 && M >= 200000) {
     if (conv3x3_db_enabled())
       conv3x3_kernel<false, 64, false, 128, true>
@@ -566,21 +597,29 @@ std::vector<at::Tensor> conv3x3_fwd_stats_impl(at::Tensor x2d, long Nn,
 }
 
 at::Tensor conv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
-                       at::Tensor w2d) {
-  return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, false)[0];
+                       at::Tensor w2d, bool nt64) {
+  return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, false, false,
+                                nt64)[0];
 }
 
 std::vector<at::Tensor> conv3x3_fwd_stats(at::Tensor x2d, long Nn, long H,
                                           long W, long stride,
-                                          at::Tensor w2d, bool banded) {
+                                          at::Tensor w2d, bool banded,
+                                          bool nt64) {
   TORCH_CHECK(!banded || (x2d.size(1) == w2d.size(0) &&
                           x2d.size(1) % 128 == 0),
               "banded conv3x3 needs Cin == Cout, both % 128");
-  return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, true, banded);
+  return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, true, banded,
+                                nt64);
 }
 
+// s2parity: stride-2 calls with even H and W run the parity-class tiling
+// (conv3x3_kernel PAR); nt64: Cin <= 64 runs the 64-wide n-tile.  Both are
+// value-for-value equal to the all-taps 128-wide loop and need the
+// double-buffered pipeline (AMDTRAIN_CONV3X3_DB=0 keeps the old loop).
 at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
-                         long stride, at::Tensor w2d, bool banded) {
+                         long stride, at::Tensor w2d, bool banded,
+                         bool s2parity, bool nt64) {
   // dy2d: [Nn*Hout*Wout, Cout]; returns dx2d [Nn*H*W, Cin]
   long Cout = dy2d.size(1), Cin = w2d.size(1) / 9;
   TORCH_CHECK(w2d.size(0) == Cout && w2d.size(1) == 9 * Cin);
@@ -624,7 +663,34 @@ at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
     const char* v = std::getenv("AMDTRAIN_CONV3X3_BK64D");
     return v && v[0] == '1';
   }();
-  if (bk64d && Cout % 64 == 0)
+  const bool par = s2parity && stride == 2 && H % 2 == 0 && W % 2 == 0 &&
+                   M < (1L << 31) && conv3x3_db_enabled();
+  const bool n64 = nt64 && Cin <= 64 && conv3x3_db_enabled();
+  if (par) {
+    // four parity classes of M/4 rows, each tiled on its own
+    const int nbmp = 4 * (int)((M / 4 + 127) / 128);
+    if (n64)
+      conv3x3_kernel<true, BK, false, 64, true, true>
+          <<<nbmp, GEMM_TPB, 0, stream>>>(
+              (const bf16*)dy2d.const_data_ptr(),
+              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
+              (int)Cout, (int)Cin, g, nbmp, 1,
+              (const bf16*)zp.const_data_ptr(), nullptr);
+    else
+      conv3x3_kernel<true, BK, false, 128, true, true>
+          <<<nbmp * nbn, GEMM_TPB, 0, stream>>>(
+              (const bf16*)dy2d.const_data_ptr(),
+              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
+              (int)Cout, (int)Cin, g, nbmp, nbn,
+              (const bf16*)zp.const_data_ptr(), nullptr);
+  } else if (n64)
+    conv3x3_kernel<true, BK, false, 64, true>
+        <<<nbm, GEMM_TPB, 0, stream>>>(
+            (const bf16*)dy2d.const_data_ptr(),
+            (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
+            (int)Cout, (int)Cin, g, nbm, 1,
+            (const bf16*)zp.const_data_ptr(), nullptr);
+  else if (bk64d && Cout % 64 == 0)
     conv3x3_kernel<true, 64><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
         (const bf16*)dy2d.const_data_ptr(),
         (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,

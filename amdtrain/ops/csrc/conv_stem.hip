@@ -10,6 +10,14 @@
 // amplification is ~940 MB/step at b256, ~0.15 ms of HBM time), then the
 // same 128x128 MFMA block structure as gemm.hip runs the math.
 //
+// The channel-padded (3 -> 8) 49-tap stem runs the C8 staging on a 64-wide
+// n-tile.  Opt-in (AMDTRAIN_STEM_S2D=1; faster, but not bit-compatible with
+// the 49-tap path) the stem runs in a width space-to-depth form
+// (conv.py stem_s2d_weight): channels 3 -> 4, two neighbouring pixels form
+// one 8-channel row, and the conv becomes 7 x 4 taps of 8 channels with
+// stride (2, 1) — K = 224 = 7 K-steps, one per kernel row (ROW4 staging),
+// on a 64-wide n-tile, with the BN-statistics partials in the epilogue.
+//
 //   fwd:   Y[m, cout] = sum_col im2col[m, col] * W2[cout, col]
 //   wgrad: dW2[cout, col] = sum_m dY[m, cout] * im2col[m, col]
 //   dgrad: dX[m=(n,h,w), ci] = sum_col2 im2colT[m, col2] * W2p[ci, col2]
@@ -29,10 +37,19 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int GEMM_TPB = 256;
 constexpr int BK = 32;
 
+__device__ __forceinline__ int xcd_swz(int bid, int nwg) {
+  constexpr int NXCD = 8;
+  if (nwg < NXCD) return bid;
+  int xcd = bid % NXCD, idx = bid / NXCD;
+  int q = nwg / NXCD, r = nwg % NXCD;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 struct StemGeom {
   int H, W, Hout, Wout;    // input / output spatial
   int KH, KW, Cin;         // filter
-  int stride, pad;
+  int stride, pad;         // along h (and along w for dgrad)
+  int sw, pw;              // forward stride / left padding along w
   int Kpad;                // padded im2col K (multiple of 32)
 };
 
@@ -59,7 +76,7 @@ __device__ __forceinline__ StemCoord stem_decode(long m, const StemGeom& g) {
   const int ho = (int)(t % g.Hout); t /= g.Hout;
   u.n_off = t * (long)g.H * g.W;
   u.hb = ho * g.stride - g.pad;
-  u.wb = wo * g.stride - g.pad;
+  u.wb = wo * g.sw - g.pw;
   return u;
 }
 
@@ -121,12 +138,13 @@ __device__ __forceinline__ void stage_im2col(
   }
 }
 
+template <int ROWS = 128>
 __device__ __forceinline__ void stage_rows(
     const bf16* __restrict__ gsrc, long ld, long row0, long rows, long koff,
     bf16* lds) {
   const int t = threadIdx.x;
 #pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
+  for (int rnd = 0; rnd < ROWS / 64; ++rnd) {
     int unit = rnd * GEMM_TPB + t;
     long row = row0 + (unit >> 2);
     if (row >= rows) row = rows - 1;
@@ -166,32 +184,69 @@ __device__ __forceinline__ void stage_im2col8(
   }
 }
 
+// ROW4 staging (Cin == 8, KW == 4, Kpad == KH*32 — the width
+// space-to-depth stem): K-step ks is exactly kernel row ks, and its 4
+// units are the 4 consecutive 16 B pixel groups wb..wb+3 of input row
+// hb + ks, i.e. 64 contiguous bytes.  A unit's column is fixed for the
+// whole K loop, so its address base and its left/right bounds test are
+// decoded once (StemRow) and the loop only steps the row: no division.
+struct StemRow {
+  long base;  // element-row index of (n, hb, wb + unit) — may be off-image
+  int hb;
+  bool wok;   // row valid and column inside [0, W)
+};
+
+__device__ __forceinline__ void stage_row4(
+    const bf16* __restrict__ x, const StemRow* ur, int ks, const StemGeom& g,
+    const bf16* __restrict__ zp, bf16* lds) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int rnd = 0; rnd < 2; ++rnd) {
+    const int unit = rnd * GEMM_TPB + t;
+    const int h = ur[rnd].hb + ks;
+    const bf16* src = zp;
+    if (ur[rnd].wok && h >= 0 && h < g.H)
+      src = x + (ur[rnd].base + (long)ks * g.W) * 8;
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)(lds + unit * 8), 16,
+        0, 0);
+  }
+}
+
 // DGRAD instantiation computes dX[m, cin] from gathered dY rows and the
 // permuted weight; operand roles mirror fwd exactly.
+// NT: output-tile width — 64 (Cout <= 64) runs a 2m x 2n wave grid of 4x2
+// fragments over [128m x 64n] with a half-size B stage, like conv3x3's.
+// stats != nullptr: also emit the BN-statistics partials [nbm][2*Cout]
+// from the fp32 accumulator (conv_epilogue_stats).
 // DB: double-buffered K-loop (gemm.hip pattern — stage ks+1's tiles while
 // ks computes, one barrier per chunk), AMDTRAIN_STEM_DB=0 reverts.
-template <bool DGRAD = false, bool C8 = false, bool DB = false>
+template <bool DGRAD = false, bool C8 = false, bool DB = false, int NT = 128,
+          bool ROW4 = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 conv_generic_fwd_kernel(const bf16* __restrict__ x,
                         const bf16* __restrict__ W2, bf16* __restrict__ Y,
                         long M, int Cout, StemGeom g, int nbm, int nbn,
-                        const bf16* __restrict__ zp) {
-  __shared__ bf16 SMEM[(DB ? 2 : 1) * 2 * 128 * BK];
-  bf16* const As = SMEM;
-  bf16* const Bs = SMEM + 128 * BK;
-  const int bid = blockIdx.x;
+                        const bf16* __restrict__ zp,
+                        float* __restrict__ stats) {
+  static_assert(!ROW4 || (C8 && !DGRAD), "ROW4 is a C8 forward staging");
+  constexpr int STG = (128 + NT) * BK;  // one A+B stage
+  constexpr int NFR = NT / 32;          // n fragments per wave
+  __shared__ bf16 SMEM[(DB ? 2 : 1) * STG];
+  const int bid = xcd_swz(blockIdx.x, nbm * nbn);
   const int bm = bid / nbn, bn = bid % nbn;
-  const long m0 = (long)bm * 128, n0 = (long)bn * 128;
+  const long m0 = (long)bm * 128, n0 = (long)bn * NT;
   const int t = threadIdx.x;
   const int wave = t / AMD_WAVE, lane = t % AMD_WAVE;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const int wm = (wave >> 1) * 64, wn = (wave & 1) * (NT / 2);
   const int fr = lane & 15, fq = lane >> 4;
 
-  f32x4 acc[4][4];
+  f32x4 acc[4][NFR];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NFR; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
   const float inv_cin = 1.f / g.Cin, inv_kw = 1.f / g.KW;
   StemCoord uc[2];
@@ -202,33 +257,45 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
     valid[rnd] = m < M;
     uc[rnd] = stem_decode<DGRAD>(valid[rnd] ? m : M - 1, g);
   }
+  StemRow ur[2];
+  if (ROW4) {
+#pragma unroll
+    for (int rnd = 0; rnd < 2; ++rnd) {
+      const int w = uc[rnd].wb + (t & 3);  // unit & 3 == t & 3
+      ur[rnd].hb = uc[rnd].hb;
+      ur[rnd].wok = valid[rnd] && w >= 0 && w < g.W;
+      ur[rnd].base = uc[rnd].n_off + (long)uc[rnd].hb * g.W + w;
+    }
+  }
 
   const int ksteps = g.Kpad / BK;
   auto stage = [&](int ks, bf16* as) {
-    if (C8)
+    if (ROW4)
+      stage_row4(x, ur, ks, g, zp, as);
+    else if (C8)
       stage_im2col8(x, uc, valid, ks * BK, g, zp, as);
     else
       stage_im2col<DGRAD>(x, uc, valid, ks * BK, g, inv_cin, inv_kw, as);
-    stage_rows(W2, g.Kpad, n0, Cout, ks * BK, as + 128 * BK);
+    stage_rows<NT>(W2, g.Kpad, n0, Cout, ks * BK, as + 128 * BK);
   };
   auto compute = [&](const bf16* as) {
     const bf16* bs = as + 128 * BK;
-    bf16x8 a[4], b[4];
+    bf16x8 a[4], b[NFR];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       a[i] = *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < NFR; ++j)
       b[j] = *(const bf16x8*)&bs[(wn + j * 16 + fr) * BK + fq * 8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < NFR; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
             a[i], b[j], acc[i][j], 0, 0, 0);
   };
   if (DB) {
-    constexpr int HB = 2 * 128 * BK;
+    constexpr int HB = STG;
     if (ksteps > 0) stage(0, SMEM);
     for (int ks = 0; ks < ksteps; ++ks) {
       bf16* const as = SMEM + (ks & 1) * HB;
@@ -247,7 +314,7 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < NFR; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         long row = m0 + wm + i * 16 + fq * 4 + r;
@@ -255,6 +322,9 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
         if (row < M && col < Cout)
           Y[row * Cout + col] = __float2bfloat16(acc[i][j][r]);
       }
+  if (stats != nullptr)
+    conv_epilogue_stats<NT>(stats, (const float*)acc, m0, M, n0, Cout, bm,
+                            wm, wn, fr, fq, SMEM);
 }
 
 // wgrad: transposed reg-staging like gemm.hip's gemm_tn, with the B chunk
@@ -371,17 +441,33 @@ conv_generic_wgrad_kernel(const bf16* __restrict__ dY,
       }
 }
 
+// stride_w == 0 / pad_w < 0 / Hout, Wout == 0: same as along h / symmetric
+// padding.  Explicit output dims serve asymmetric padding (only the top /
+// left amounts enter the gather; the bottom / right are implied).
 static StemGeom make_geom(long H, long W, long KH, long KW, long Cin,
-                          long stride, long pad) {
+                          long stride, long pad, long stride_w = 0,
+                          long pad_w = -1, long Hout = 0, long Wout = 0) {
   StemGeom g;
   g.H = (int)H; g.W = (int)W;
-  g.Hout = (int)((H + 2 * pad - KH) / stride + 1);
-  g.Wout = (int)((W + 2 * pad - KW) / stride + 1);
+  g.sw = (int)(stride_w > 0 ? stride_w : stride);
+  g.pw = (int)(pad_w >= 0 ? pad_w : pad);
+  g.Hout = (int)(Hout > 0 ? Hout : (H + 2 * pad - KH) / stride + 1);
+  g.Wout = (int)(Wout > 0 ? Wout : (W + 2 * g.pw - KW) / g.sw + 1);
   g.KH = (int)KH; g.KW = (int)KW; g.Cin = (int)Cin;
   g.stride = (int)stride; g.pad = (int)pad;
   int K = (int)(KH * KW * Cin);
   g.Kpad = (K + 31) / 32 * 32;
   return g;
+}
+
+template <bool DGRAD, bool C8, bool DBUF, int NT = 128, bool ROW4 = false>
+static void stem_launch(int grid, hipStream_t stream, const bf16* x,
+                        const bf16* w2, bf16* y, long M, int Cout,
+                        const StemGeom& g, int nbm, int nbn, const bf16* zp,
+                        float* stats) {
+  conv_generic_fwd_kernel<DGRAD, C8, DBUF, NT, ROW4>
+      <<<grid, GEMM_TPB, 0, stream>>>(x, w2, y, M, Cout, g, nbm, nbn, zp,
+                                      stats);
 }
 
 static at::Tensor stem_zero_page(const at::Tensor& like) {
@@ -404,13 +490,22 @@ static bool stem_db_enabled() {
 }
 
 // x2d: [N*H*W, Cin] bf16 NHWC rows; w2: [Cout, Kpad] (host-padded).
-// Cin == 8 (channel-padded stem) takes the vectorized tap-gather staging.
-at::Tensor conv_generic_fwd(at::Tensor x2d, long Nn, long H, long W,
-                            long KH, long KW, long stride, long pad,
-                            at::Tensor w2) {
+// Cin == 8 (channel-padded stem) takes the vectorized tap-gather staging;
+// with KW == 4 and no K padding on top (the width space-to-depth stem) the
+// division-free row staging.  tile64 runs either Cin == 8 staging on the
+// 64-wide n-tile when Cout <= 64 (per-element K order unchanged, so y is
+// identical to the 128-wide tile's).  want_stats adds the BN-statistics
+// partials [nbm][2*Cout].
+static std::vector<at::Tensor> conv_generic_fwd_impl(
+    at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
+    long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
+    bool want_stats, bool tile64) {
   TORCH_CHECK(x2d.is_cuda() && x2d.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(x2d.is_contiguous() && w2.is_contiguous());
   long Cin = x2d.size(1), Cout = w2.size(0);
-  auto g = make_geom(H, W, KH, KW, Cin, stride, pad);
+  TORCH_CHECK(x2d.size(0) == Nn * H * W);
+  auto g = make_geom(H, W, KH, KW, Cin, stride, pad, stride_w, pad_w, Hout,
+                     Wout);
   TORCH_CHECK(w2.size(1) == g.Kpad, "weight must be K-padded to ", g.Kpad);
   long M = Nn * g.Hout * g.Wout;
   auto y = at::empty({M, Cout}, x2d.options());
@@ -418,32 +513,64 @@ at::Tensor conv_generic_fwd(at::Tensor x2d, long Nn, long H, long W,
   auto stream = at::cuda::getCurrentCUDAStream();
   auto zp = stem_zero_page(x2d);
   const bool db = stem_db_enabled();
-  if (Cin == 8 && g.Kpad == (KH * KW * 8 + 31) / 32 * 32) {
-    if (db)
-      conv_generic_fwd_kernel<false, true, true>
-          <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-              (const bf16*)x2d.const_data_ptr(),
-              (const bf16*)w2.const_data_ptr(), (bf16*)y.data_ptr(), M,
-              (int)Cout, g, nbm, nbn, (const bf16*)zp.const_data_ptr());
-    else
-      conv_generic_fwd_kernel<false, true>
-          <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-              (const bf16*)x2d.const_data_ptr(),
-              (const bf16*)w2.const_data_ptr(), (bf16*)y.data_ptr(), M,
-              (int)Cout, g, nbm, nbn, (const bf16*)zp.const_data_ptr());
-  } else if (db)
-    conv_generic_fwd_kernel<false, false, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)x2d.const_data_ptr(),
-            (const bf16*)w2.const_data_ptr(), (bf16*)y.data_ptr(), M,
-            (int)Cout, g, nbm, nbn, (const bf16*)zp.const_data_ptr());
+  const bool c8 = Cin == 8 && g.Kpad == (KH * KW * 8 + 31) / 32 * 32;
+  const bool row4 = c8 && KW == 4 && g.Kpad == KH * 32;
+  const bool t64 = tile64 && Cout <= 64;
+  TORCH_CHECK(!want_stats || c8, "conv_generic stats need the C8 kernel");
+  at::Tensor stats;
+  float* sp = nullptr;
+  if (want_stats) {
+    stats = at::empty({nbm, 2 * Cout}, x2d.options().dtype(at::kFloat));
+    sp = stats.data_ptr<float>();
+  }
+  const bf16* xp = (const bf16*)x2d.const_data_ptr();
+  const bf16* wp = (const bf16*)w2.const_data_ptr();
+  const bf16* zpp = (const bf16*)zp.const_data_ptr();
+  bf16* yp = (bf16*)y.data_ptr();
+  const int grid = nbm * nbn, co = (int)Cout;
+  if (c8 && row4 && t64 && db)
+    stem_launch<false, true, true, 64, true>(grid, stream, xp, wp, yp, M, co,
+                                             g, nbm, nbn, zpp, sp);
+  else if (c8 && row4 && t64)
+    stem_launch<false, true, false, 64, true>(grid, stream, xp, wp, yp, M, co,
+                                              g, nbm, nbn, zpp, sp);
+  else if (c8 && t64 && db)  // 49-tap stem: same K order, half the MFMAs
+    stem_launch<false, true, true, 64>(grid, stream, xp, wp, yp, M, co, g,
+                                       nbm, nbn, zpp, sp);
+  else if (c8 && t64)
+    stem_launch<false, true, false, 64>(grid, stream, xp, wp, yp, M, co, g,
+                                        nbm, nbn, zpp, sp);
+  else if (c8 && db)
+    stem_launch<false, true, true>(grid, stream, xp, wp, yp, M, co, g, nbm,
+                                   nbn, zpp, sp);
+  else if (c8)
+    stem_launch<false, true, false>(grid, stream, xp, wp, yp, M, co, g, nbm,
+                                    nbn, zpp, sp);
+  else if (db)
+    stem_launch<false, false, true>(grid, stream, xp, wp, yp, M, co, g, nbm,
+                                    nbn, zpp, sp);
   else
-    conv_generic_fwd_kernel<false><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)x2d.const_data_ptr(), (const bf16*)w2.const_data_ptr(),
-        (bf16*)y.data_ptr(), M, (int)Cout, g, nbm, nbn,
-        (const bf16*)zp.const_data_ptr());
+    stem_launch<false, false, false>(grid, stream, xp, wp, yp, M, co, g, nbm,
+                                     nbn, zpp, sp);
   CHECK_CUDA_OK();
-  return y;
+  if (want_stats) return {y, stats};
+  return {y};
+}
+
+at::Tensor conv_generic_fwd(at::Tensor x2d, long Nn, long H, long W,
+                            long KH, long KW, long stride, long pad,
+                            at::Tensor w2, long stride_w, long pad_w,
+                            long Hout, long Wout, bool tile64) {
+  return conv_generic_fwd_impl(x2d, Nn, H, W, KH, KW, stride, pad, w2,
+                               stride_w, pad_w, Hout, Wout, false, tile64)[0];
+}
+
+std::vector<at::Tensor> conv_generic_fwd_stats(
+    at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
+    long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
+    bool tile64) {
+  return conv_generic_fwd_impl(x2d, Nn, H, W, KH, KW, stride, pad, w2,
+                               stride_w, pad_w, Hout, Wout, true, tile64);
 }
 
 // dy2d: [N*Hout*Wout, Cout]; w2p: [Cin, pad32(KH*KW*Cout)] (weight permuted
@@ -467,12 +594,13 @@ at::Tensor conv_generic_dgrad(at::Tensor dy2d, at::Tensor w2p, long Nn,
         <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
             (const bf16*)dy2d.const_data_ptr(),
             (const bf16*)w2p.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-            (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr());
+            (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr(),
+            nullptr);
   else
     conv_generic_fwd_kernel<true><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
         (const bf16*)dy2d.const_data_ptr(),
         (const bf16*)w2p.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-        (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr());
+        (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr(), nullptr);
   CHECK_CUDA_OK();
   return dx;
 }

@@ -84,10 +84,11 @@ at::Tensor transpose_2d(at::Tensor x);
 
 // conv3x3.hip
 at::Tensor conv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
-                       at::Tensor w2d);
+                       at::Tensor w2d, bool nt64);
 std::vector<at::Tensor> conv3x3_fwd_stats(at::Tensor x2d, long Nn, long H,
                                           long W, long stride,
-                                          at::Tensor w2d, bool banded);
+                                          at::Tensor w2d, bool banded,
+                                          bool nt64);
 std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B);
 
 // gemm8p.hip
@@ -96,21 +97,29 @@ at::Tensor gemm_bt_8p3(at::Tensor A, at::Tensor B);
 at::Tensor conv3x3_8p(at::Tensor A2d, long Nn, long H, long W, long stride,
                       at::Tensor w2d, bool dgrad);
 at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
-                         long stride, at::Tensor w2d, bool banded);
+                         long stride, at::Tensor w2d, bool banded,
+                         bool s2parity, bool nt64);
 at::Tensor conv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
                          long W, long stride);
 
 // wgrad.hip
 at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
                      long W, long stride, long gmode, long kh, long kw,
-                     long pad);
+                     long pad, long stride_w, long pad_w, long Hout,
+                     long Wout);
 at::Tensor tn2_wgrad_banded(at::Tensor dY, at::Tensor X, long Nn, long H,
                             long W, long stride);
 at::Tensor tr16_probe(at::Tensor in);
 
 // conv_stem.hip
 at::Tensor conv_generic_fwd(at::Tensor x2d, long Nn, long H, long W, long KH,
-                            long KW, long stride, long pad, at::Tensor w2);
+                            long KW, long stride, long pad, at::Tensor w2,
+                            long stride_w, long pad_w, long Hout, long Wout,
+                            bool tile64);
+std::vector<at::Tensor> conv_generic_fwd_stats(
+    at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
+    long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
+    bool tile64);
 at::Tensor conv_generic_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn,
                               long H, long W, long KH, long KW, long stride,
                               long pad);
@@ -172,25 +181,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bt_strided", &gemm_bt_strided);
   m.def("gemm_tn_strided", &gemm_tn_strided);
   m.def("transpose_2d", &transpose_2d);
-  m.def("conv3x3_fwd", &conv3x3_fwd);
+  m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
+        py::arg("nt64") = true);
   m.def("conv3x3_fwd_stats", &conv3x3_fwd_stats, py::arg("x2d"),
         py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("stride"),
-        py::arg("w2d"), py::arg("banded") = false);
+        py::arg("w2d"), py::arg("banded") = false, py::arg("nt64") = true);
   m.def("gemm_bt_stats", &gemm_bt_stats);
   m.def("gemm_bt_8p", &gemm_bt_8p);
   m.def("gemm_bt_8p3", &gemm_bt_8p3);
   m.def("conv3x3_8p", &conv3x3_8p);
   m.def("conv3x3_dgrad", &conv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
-        py::arg("banded") = false);
+        py::arg("banded") = false, py::arg("s2parity") = true,
+        py::arg("nt64") = true);
   m.def("conv3x3_wgrad", &conv3x3_wgrad);
   m.def("tn2_wgrad", &tn2_wgrad, py::arg("dY"), py::arg("X"),
         py::arg("taps") = 1, py::arg("Nn") = 0, py::arg("H") = 0,
         py::arg("W") = 0, py::arg("stride") = 1, py::arg("gmode") = 0,
-        py::arg("kh") = 3, py::arg("kw") = 3, py::arg("pad") = 1);
+        py::arg("kh") = 3, py::arg("kw") = 3, py::arg("pad") = 1,
+        py::arg("stride_w") = 0, py::arg("pad_w") = -1, py::arg("Hout") = 0,
+        py::arg("Wout") = 0);
   m.def("tn2_wgrad_banded", &tn2_wgrad_banded);
   m.def("tr16_probe", &tr16_probe);
-  m.def("conv_generic_fwd", &conv_generic_fwd);
+  m.def("conv_generic_fwd", &conv_generic_fwd, py::arg("x2d"),
+        py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("KH"),
+        py::arg("KW"), py::arg("stride"), py::arg("pad"), py::arg("w2"),
+        py::arg("stride_w") = 0, py::arg("pad_w") = -1, py::arg("Hout") = 0,
+        py::arg("Wout") = 0, py::arg("tile64") = false);
+  m.def("conv_generic_fwd_stats", &conv_generic_fwd_stats, py::arg("x2d"),
+        py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("KH"),
+        py::arg("KW"), py::arg("stride"), py::arg("pad"), py::arg("w2"),
+        py::arg("stride_w") = 0, py::arg("pad_w") = -1, py::arg("Hout") = 0,
+        py::arg("Wout") = 0, py::arg("tile64") = false);
   m.def("conv_generic_wgrad", &conv_generic_wgrad);
   m.def("conv_generic_dgrad", &conv_generic_dgrad);
   m.def("max_pool_3x3_s2_fwd", &max_pool_3x3_s2_fwd, py::arg("x"),

@@ -60,20 +60,40 @@ __device__ __forceinline__ int xcd_swz_tn2(int bid, int nwg) {
 }
 
 struct TnGeom {
-  int H, W, Hout, Wout, stride;
+  int H, W, Hout, Wout, stride;  // stride / pad: along h
   int kh, kw, pad;  // filter geometry (3,3,1 for the bottleneck 3x3 convs)
+  int sw, pw;       // stride / left padding along w
 };
 
-// generic conv forward gather: output row m=(n,ho,wo) + tap -> X row or -1
-__device__ __forceinline__ long tn2_gather_conv(long m, int tap,
-                                                const TnGeom& g) {
+// generic conv forward gather, split in two so the (n, ho, wo) decode of a
+// staged row — two 64-bit div/mod pairs — runs once per row, not once per
+// 16 B unit: output row m -> tap-0 input coordinates ...
+struct TnRow {
+  long n_off;  // n * H * W
+  int hb, wb;  // may be negative / off-image
+};
+
+__device__ __forceinline__ TnRow tn2_decode_row(long m, const TnGeom& g) {
+  TnRow r;
   long t = m;
   const int wo = (int)(t % g.Wout); t /= g.Wout;
   const int ho = (int)(t % g.Hout); t /= g.Hout;
-  const int h = ho * g.stride - g.pad + tap / g.kw;
-  const int w = wo * g.stride - g.pad + tap % g.kw;
+  r.n_off = t * (long)g.H * g.W;
+  r.hb = ho * g.stride - g.pad;
+  r.wb = wo * g.sw - g.pw;
+  return r;
+}
+
+// ... + tap -> X row or -1
+__device__ __forceinline__ long tn2_gather_tap(const TnRow& r, int tap,
+                                               const TnGeom& g) {
+  // 3- and 4-wide filters (every 3x3 conv, the space-to-depth stem) divide
+  // by a constant
+  const int kh = g.kw == 3 ? tap / 3 : g.kw == 4 ? tap >> 2 : tap / g.kw;
+  const int h = r.hb + kh;
+  const int w = r.wb + tap - kh * g.kw;
   if (h < 0 || h >= g.H || w < 0 || w >= g.W) return -1;
-  return (t * g.H + h) * g.W + w;
+  return r.n_off + (long)h * g.W + w;
 }
 
 // strided-1x1 gather: compact output row m=(n,ho,wo) -> input row
@@ -121,10 +141,22 @@ __device__ __forceinline__ void stage_tn2(
   const int r = lane >> 5, q = (lane >> 3) & 3, j = (lane >> 1) & 3;
   const int c_half = (lane & 1) * 8;
   const int mfrag = q * 8 + r * 4 + j;  // m offset within the 32-row block
+  // a thread's rows differ only by the 32-row block: decode each once
+  TnRow rows[MC / 32];
+  if (MODE == 2) {
+#pragma unroll
+    for (int mb = 0; mb < MC / 32; ++mb) {
+      const long m = m0 + mb * 32 + mfrag;
+      rows[mb] = tn2_decode_row(m < M ? m : M - 1, geo);
+    }
+  }
 #pragma unroll
   for (int ss = 0; ss < SUBTILES / NWAVES; ++ss) {
     const int s = ss * NWAVES + wave;
-    const int mb = s / (NCOLS / 16);         // 32-row block
+    // 32-row block: a compile-time constant per unrolled ss (a wave round
+    // never straddles two blocks), so rows[] stays in registers
+    static_assert((NCOLS / 16) % NWAVES == 0, "wave round spans m-blocks");
+    const int mb = (ss * NWAVES) / (NCOLS / 16);
     const int cs = (s % (NCOLS / 16)) * 16;  // subtile column base
     const int mloc = mb * 32 + mfrag;
     const long m = m0 + mloc;
@@ -136,8 +168,11 @@ __device__ __forceinline__ void stage_tn2(
       } else if (MODE == 1) {
         src = g + tn2_gather_stride(m, geo) * (long)ld + col;
       } else {
-        const int tap = col / cin;  // unit never spans taps (cin % 8 == 0)
-        const long row = tn2_gather_conv(m, tap, geo);
+        // unit never spans taps (cin % 8 == 0); power-of-two channel
+        // counts (all of ResNet's, and the stem's 8) shift instead
+        const int tap = (cin & (cin - 1)) == 0 ? col >> (__ffs(cin) - 1)
+                                               : col / cin;
+        const long row = tn2_gather_tap(rows[mb], tap, geo);
         if (row >= 0) src = g + row * (long)ld + (col - tap * cin);
       }
     }
@@ -424,12 +459,14 @@ void tn2_launch(const at::Tensor& dY, const at::Tensor& X, at::Tensor& out,
 }  // namespace
 
 // Unified TN wgrad v2.  gmode: 0 = plain rows (1x1 s1 / linear), 1 =
-// strided-1x1 row gather, 2 = conv3x3 tap gather (taps*Cin columns).
+// strided-1x1 row gather, 2 = conv tap gather (taps*Cin columns; kh x kw
+// filter, stride / pad along h, stride_w / pad_w along w).
 // Returns fp32 [N, taps*Cin]; bitwise deterministic (fixed split + ordered
 // collapse).
 at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
                      long W, long stride, long gmode, long kh, long kw,
-                     long pad) {
+                     long pad, long stride_w, long pad_w, long Hout,
+                     long Wout) {
   TORCH_CHECK(dY.is_cuda() && dY.scalar_type() == at::kBFloat16 &&
               X.scalar_type() == at::kBFloat16);
   auto Yc = dY.contiguous();
@@ -439,17 +476,23 @@ at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
   const int Cin = (int)Xc.size(1);
   const int K9 = (int)(taps * Cin);
   TORCH_CHECK(Cin % 8 == 0 && N % 8 == 0);
-  TnGeom geo{0, 0, 0, 0, 1, 3, 3, 1};
+  TnGeom geo{0, 0, 0, 0, 1, 3, 3, 1, 1, 1};
   if (gmode == 1) {
     long Hout = (H + stride - 1) / stride, Wout = (W + stride - 1) / stride;
     TORCH_CHECK(M == Nn * Hout * Wout);
-    geo = TnGeom{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride, 1, 1, 0};
+    geo = TnGeom{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride, 1, 1, 0,
+                 (int)stride, 0};
   } else if (gmode == 2) {
-    long Hout = (H + 2 * pad - kh) / stride + 1;
-    long Wout = (W + 2 * pad - kw) / stride + 1;
+    // stride_w == 0 / pad_w < 0 / Hout, Wout == 0: same as along h,
+    // symmetric padding (explicit output dims serve asymmetric padding)
+    const long sw = stride_w > 0 ? stride_w : stride;
+    const long pw = pad_w >= 0 ? pad_w : pad;
+    if (Hout <= 0) Hout = (H + 2 * pad - kh) / stride + 1;
+    if (Wout <= 0) Wout = (W + 2 * pw - kw) / sw + 1;
     TORCH_CHECK(M == Nn * Hout * Wout && taps == kh * kw);
+    TORCH_CHECK(Xc.size(0) == Nn * H * W);
     geo = TnGeom{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride,
-                 (int)kh, (int)kw, (int)pad};
+                 (int)kh, (int)kw, (int)pad, (int)sw, (int)pw};
   } else {
     TORCH_CHECK(M == Xc.size(0));
   }
@@ -460,14 +503,21 @@ at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
 
   // config: (2,2) 128x128 tile MC=64 default; skinny-N with wide K -> (1,4);
   // skinny-K with tall N -> (4,1) (both MC=32 to keep 2 blocks/CU in LDS)
-  if (N < 128 && K9 >= 256) {
+  // thin-channel tap gather (the stem, Cin = 8): also below K9 = 256, where
+  // the 256-wide k-tile of (1,4,32) holds all of K9 and dY is staged once
+  if (N < 128 && (K9 >= 256 || (gmode == 2 && Cin < 32))) {
     // skinny-N conv wgrad: the (2,2,64) tile zero-pads the N half but its
     // MC=64 pipeline beats the fully-dense (1,4,32) config (which is
     // issue-bound at 16 MFMA/barrier) for layer-1-class shapes; the
     // channel-padded STEM (Cin=8) measured the other way (1.55 vs 1.78 ms
     // at b512) — its 16x-redundant tap gather prefers the narrower k-tile.
-    // A/B via AMDTRAIN_TN2_14
+    // A/B via AMDTRAIN_TN2_14.  The space-to-depth stem (28 taps, K9 = 224)
+    // fits the 256-wide k-tile of (1,4,32) whole, so dY is staged once:
+    // 0.63 ms against 0.82 ms on (2,2,64) and 1.45 ms for the 49-tap form
+    // (b512, tools/bench_wgrad.py --stem; AMDTRAIN_TN2_STEM22 forces (2,2,64))
     if (gmode == 2 && Cin >= 32 && std::getenv("AMDTRAIN_TN2_14") == nullptr)
+      tn2_launch<2, 2, 2, 64>(Yc, Xc, out, M, N, K9, Cin, geo, target, stream);
+    else if (gmode == 2 && std::getenv("AMDTRAIN_TN2_STEM22") != nullptr)
       tn2_launch<2, 2, 2, 64>(Yc, Xc, out, M, N, K9, Cin, geo, target, stream);
     else if (gmode == 2)
       tn2_launch<2, 1, 4, 32>(Yc, Xc, out, M, N, K9, Cin, geo, target, stream);
@@ -536,7 +586,8 @@ at::Tensor tn2_wgrad_banded(at::Tensor dY, at::Tensor X, long Nn, long H,
   TORCH_CHECK(N == Cin && N % 128 == 0);
   long Hout = (H + 2 - 3) / stride + 1, Wout = (W + 2 - 3) / stride + 1;
   TORCH_CHECK(M == Nn * Hout * Wout);
-  TnGeom geo{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride, 3, 3, 1};
+  TnGeom geo{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride, 3, 3, 1,
+             (int)stride, 1};
   auto out = at::empty({(long)N, (long)9 * 128},
                        Yc.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();

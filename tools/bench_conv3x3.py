@@ -1,5 +1,9 @@
 """A/B: conv3x3 128x128 kernels vs the 256x256 (8p3) structure on
-layer3/layer4 shapes, refchecked vs F.conv2d."""
+layer3/layer4 shapes, refchecked vs F.conv2d.
+
+``--dgrad-split [B]`` instead times the dgrad (and the layer-1 forward) of
+every ResNet-50 conv3x3 site at batch B, stride 1 and stride 2 apart, with
+the parity-class tiles / the 64-wide n-tile switched off and on."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -67,7 +71,57 @@ def run(n, cin, cout, hw, stride=1):
                   flush=True)
 
 
+def dgrad_split(n):
+    """Per-shape dgrad times: (sites per step, cin, cout, hw, stride)."""
+    tot = {"off": 0.0, "on": 0.0}
+    for cnt, cin, cout, hw, stride in [
+            (3, 64, 64, 56, 1),
+            (1, 128, 128, 56, 2), (3, 128, 128, 28, 1),
+            (1, 256, 256, 28, 2), (5, 256, 256, 14, 1),
+            (1, 512, 512, 14, 2), (2, 512, 512, 7, 1)]:
+        torch.manual_seed(0)
+        ho = (hw + 2 - 3) // stride + 1
+        gy2d = torch.randn(n * ho * ho, cout, device="cuda").bfloat16()
+        w2d = (torch.randn(cout, 9 * cin, device="cuda")
+               * (9 * cin) ** -0.5).bfloat16()
+        off = lambda: _C.conv3x3_dgrad(gy2d, n, hw, hw, stride, w2d, False,
+                                       False, False)
+        on = lambda: _C.conv3x3_dgrad(gy2d, n, hw, hw, stride, w2d, False,
+                                      True, True)
+        same = torch.equal(off(), on())
+        # interleave the two variants; keep the faster of two rounds each
+        t = {"off": 1e9, "on": 1e9}
+        for _ in range(2):
+            t["off"] = min(t["off"], time_fn(off))
+            t["on"] = min(t["on"], time_fn(on))
+        flops = 2.0 * n * ho * ho * cout * 9 * cin
+        print(f"dgrad x{cnt} c={cin}->{cout} hw={hw} s={stride}: "
+              f"off {t['off']*1e6:7.1f} us ({flops/t['off']/1e12:6.1f} TF) | "
+              f"on {t['on']*1e6:7.1f} us ({flops/t['on']/1e12:6.1f} TF) "
+              f"{'equal' if same else 'DIFFERENT'}", flush=True)
+        for k in tot:
+            tot[k] += cnt * t[k]
+    print(f"dgrad per step (weighted): off {tot['off']*1e6:.0f} us  "
+          f"on {tot['on']*1e6:.0f} us")
+    # layer-1 forward, 128- vs 64-wide n-tile
+    cin = cout = 64
+    hw = 56
+    x2d = torch.randn(n * hw * hw, cin, device="cuda").bfloat16()
+    w2d = (torch.randn(cout, 9 * cin, device="cuda")
+           * (9 * cin) ** -0.5).bfloat16()
+    f128 = lambda: _C.conv3x3_fwd_stats(x2d, n, hw, hw, 1, w2d, False, False)
+    f64 = lambda: _C.conv3x3_fwd_stats(x2d, n, hw, hw, 1, w2d, False, True)
+    same = all(torch.equal(a, b) for a, b in zip(f128(), f64()))
+    t128 = min(time_fn(f128), time_fn(f128))
+    t64 = min(time_fn(f64), time_fn(f64))
+    print(f"fwd+stats x3 c=64->64 hw=56 s=1: NT128 {t128*1e6:7.1f} us | "
+          f"NT64 {t64*1e6:7.1f} us {'equal' if same else 'DIFFERENT'}")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "--dgrad-split":
+        dgrad_split(int(sys.argv[2]) if len(sys.argv) > 2 else 512)
+        sys.exit(0)
     run(512, 256, 256, 14)   # layer3 3x3 (K=2304)
     run(512, 512, 512, 7)    # layer4 3x3 (K=4608)
     run(512, 128, 128, 28)   # layer2 3x3 (K=1152)

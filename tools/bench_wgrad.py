@@ -1,6 +1,11 @@
 """Micro-benchmark: round-1 TN wgrad kernels (gemm_tn / conv3x3_wgrad,
 per-tap + atomics) vs the v2 tr-read core (tn2_wgrad) on the ResNet-50
-b512 wgrad shapes, refchecked vs fp32 matmul."""
+b512 wgrad shapes, refchecked vs fp32 matmul.
+
+``--stem`` instead times the 7x7 stem at batch BENCH_B: the 49-tap
+channel-padded forward and wgrad against the width space-to-depth form,
+whose wgrad runs on the (1,4,32) and, with AMDTRAIN_TN2_STEM22, the
+(2,2,64) wave grid."""
 import os
 import sys
 import time
@@ -90,5 +95,51 @@ def main():
           f"new {tot_new*1e3:.2f} ms  speedup x{tot_old/tot_new:.2f}")
 
 
+def run_stem():
+    import torch.nn.functional as F
+    from amdtrain.ops.conv import stem_s2d_input, stem_s2d_weight
+    torch.manual_seed(0)
+    H = 224
+    Ho = (H + 6 - 7) // 2 + 1
+    M = B * Ho * Ho
+    x = torch.randn(B, H, H, 3, device="cuda").bfloat16()
+    w = (torch.randn(64, 3, 7, 7, device="cuda") * 147 ** -0.5).bfloat16()
+    gy = torch.randn(M, 64, device="cuda").bfloat16()
+    x8 = F.pad(x, (0, 5)).view(B * H * H, 8)
+    w8 = F.pad(F.pad(w.permute(0, 2, 3, 1), (0, 5)).reshape(64, 392),
+               (0, 24))
+    xs = stem_s2d_input(x).view(B * H * (H // 2), 8)
+    ws = stem_s2d_weight(w).reshape(64, 224)
+    f_old = lambda: _C.conv_generic_fwd(x8, B, H, H, 7, 7, 2, 3, w8)
+    f_new = lambda: _C.conv_generic_fwd_stats(xs, B, H, H // 2, 7, 4, 2, 3, ws,
+                                              1, 2, Ho, Ho, True)
+    g_old = lambda: _C.tn2_wgrad(gy, x8, 49, B, H, H, 2, 2, 7, 7, 3)
+    g_new = lambda: _C.tn2_wgrad(gy, xs, 28, B, H, H // 2, 2, 2, 7, 4, 3,
+                                 1, 2, Ho, Ho)
+    f_old64 = lambda: _C.conv_generic_fwd(x8, B, H, H, 7, 7, 2, 3, w8,
+                                          0, -1, 0, 0, True)
+    print("stem fwd 49-tap NT64 vs NT128:",
+          "equal" if torch.equal(f_old64(), f_old()) else "DIFFERENT")
+    err = (f_new()[0].float() - f_old().float()).abs().max().item()
+    print(f"stem fwd s2d vs 49-tap: max diff {err:.4f}")
+    flops = 2.0 * M * 64 * 147
+    for tag, fn in [("fwd 49-tap K=416 NT128", f_old),
+                    ("fwd 49-tap K=416 NT64", f_old64),
+                    ("fwd s2d K=224 NT64 +stats", f_new),
+                    ("wgrad 49-tap (1,4,32) nbk=2", g_old),
+                    ("wgrad s2d (1,4,32) nbk=1", g_new)]:
+        t = min(time_fn(fn), time_fn(fn))
+        print(f"{tag:30s} {t*1e6:8.1f} us  ({flops/t/1e12:6.1f} useful TF)",
+              flush=True)
+    os.environ["AMDTRAIN_TN2_STEM22"] = "1"
+    t = min(time_fn(g_new), time_fn(g_new))
+    del os.environ["AMDTRAIN_TN2_STEM22"]
+    print(f"{'wgrad s2d (2,2,64) nbk=2':30s} {t*1e6:8.1f} us  "
+          f"({flops/t/1e12:6.1f} useful TF)")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "--stem":
+        run_stem()
+    else:
+        main()
