@@ -60,6 +60,23 @@ def _nt64_enabled() -> bool:
     return os.environ.get("AMDTRAIN_CONV3X3_NT64", "1") == "1"
 
 
+def _epilogue_mode() -> int:
+    """bf16 C-store epilogue of the MFMA kernels (csrc/common.h):
+    AMDTRAIN_EPILOGUE=0 per-element predicated 2-byte stores, 1 lean
+    addressing on interior tiles, 2 lean addressing + 16-byte stores.  All
+    modes give the same bits.  Read on every call and passed down as an
+    argument, so one process can compare them.  Unset -> -1: every kernel
+    runs its measured default (2, except the dual-n-tile 1x1 GEMM: 1; see
+    docs/KERNELS.md)."""
+    v = os.environ.get("AMDTRAIN_EPILOGUE")
+    if v is None or v == "":
+        return -1
+    mode = int(v)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"AMDTRAIN_EPILOGUE must be 0, 1 or 2, got {v!r}")
+    return mode
+
+
 def _wgrad2_enabled() -> bool:
     """tn2_wgrad (wgrad.hip): tr-read TN core — single launch for all 9
     conv3x3 taps, no atomics, bitwise deterministic.  Default on;
@@ -159,14 +176,16 @@ class _Conv1x1(torch.autograd.Function):
             # even-row gather happens inside the A staging (no copy); the
             # full x2d is saved — it is the same tensor the sibling conv of
             # the residual block already saves, so no extra memory
-            y2d = e.gemm_bt_strided(x2d, w2d, n, h, w, stride)
+            y2d = e.gemm_bt_strided(x2d, w2d, n, h, w, stride,
+                                    _epilogue_mode())
             ho = (h + stride - 1) // stride
             wo = (w + stride - 1) // stride
         elif _fuse_stats_enabled():
-            y2d, stats = e.gemm_bt_stats(x2d, w2d)
+            y2d, stats = e.gemm_bt_stats(x2d, w2d, _epilogue_mode())
             ho, wo = h, w
         else:
-            y2d = e.gemm_bt(x2d, w2d, False)
+            y2d = e.gemm_bt(x2d, w2d, False, None, None,
+                            _epilogue_mode())
             ho, wo = h, w
         ctx.save_for_backward(x2d, w2d)
         ctx.meta = (n, cin, h, w, stride, ho, wo, cout)
@@ -186,7 +205,8 @@ class _Conv1x1(torch.autograd.Function):
         gy2d = _rows(gy).to(torch.bfloat16)
         # dgrad: dX = dY x W  (BT form with pre-transposed weight)
         wT = e.transpose_2d(w2d)                      # [Cin, Cout]
-        dx2d = e.gemm_bt(gy2d, wT, False)             # [R_sub, Cin] bf16
+        dx2d = e.gemm_bt(gy2d, wT, False, None, None,
+                         _epilogue_mode())      # [R_sub, Cin] bf16
         if stride > 1:
             cell = ctx.cell
             if (stride == 2 and cell is not None and cell.armed
@@ -240,9 +260,11 @@ class _Conv3x3(torch.autograd.Function):
         nt64 = _nt64_enabled()
         if _fuse_stats_enabled():
             y2d, stats = e.conv3x3_fwd_stats(x2d, n, h, w, stride, w2d,
-                                             False, nt64)
+                                             False, nt64,
+                                             _epilogue_mode())
         else:
-            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, nt64)
+            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, nt64,
+                                _epilogue_mode())
             stats = torch.empty(0, device=x.device)
         ctx.save_for_backward(x2d, w2d)
         ctx.meta = (n, cin, h, w, stride, cout)
@@ -261,7 +283,8 @@ class _Conv3x3(torch.autograd.Function):
         gy = grad_y.contiguous(memory_format=torch.channels_last)
         gy2d = _rows(gy).to(torch.bfloat16)
         dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, False,
-                               _s2parity_enabled(), _nt64_enabled())
+                               _s2parity_enabled(), _nt64_enabled(),
+                               _epilogue_mode())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         # [Cout, 9*Cin] f32 — single-launch tap-gather TN (wgrad.hip)
         dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2) \
@@ -319,9 +342,11 @@ class _ConvGrouped3x3(torch.autograd.Function):
         banded = (cin == cout and cin % 128 == 0)
         if _fuse_stats_enabled():
             y2d, stats = e.conv3x3_fwd_stats(x2d, n, h, w, stride, w2d,
-                                             banded, _nt64_enabled())
+                                             banded, _nt64_enabled(),
+                                             _epilogue_mode())
         else:
-            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, _nt64_enabled())
+            y2d = e.conv3x3_fwd(x2d, n, h, w, stride, w2d, _nt64_enabled(),
+                                _epilogue_mode())
             stats = torch.empty(0, device=x.device)
         ctx.save_for_backward(x2d, w2d)
         ctx.meta = (n, cin, h, w, stride, cout, groups, banded)
@@ -342,7 +367,8 @@ class _ConvGrouped3x3(torch.autograd.Function):
         gy = grad_y.contiguous(memory_format=torch.channels_last)
         gy2d = _rows(gy).to(torch.bfloat16)
         dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, banded,
-                               _s2parity_enabled(), _nt64_enabled())
+                               _s2parity_enabled(), _nt64_enabled(),
+                               _epilogue_mode())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         if banded and _wgrad2_enabled():
             # compact band [Cout, 9, 128]: extract the group diagonal of
@@ -441,7 +467,8 @@ class _ConvGeneric(torch.autograd.Function):
             x8 = stem_s2d_input(x2d.view(n, h, w, cin)) \
                 .view(n * h * (w // 2), 8)
             w2 = stem_s2d_weight(weight).reshape(cout, 224)
-            geom = (n, h, w // 2, 7, 4, 2, 3, w2, 1, 2, ho, wo, True)
+            geom = (n, h, w // 2, 7, 4, 2, 3, w2, 1, 2, ho, wo, True,
+                    _epilogue_mode())
             if _fuse_stats_enabled():
                 y2d, stats = e.conv_generic_fwd_stats(x8, *geom)
             else:
@@ -467,7 +494,7 @@ class _ConvGeneric(torch.autograd.Function):
         if kpad != k:
             w2 = torch.nn.functional.pad(w2, (0, kpad - k))
         y2d = e.conv_generic_fwd(x2d, n, h, w, kh, kw, stride, pad, w2,
-                                 0, -1, 0, 0, nt64)
+                                 0, -1, 0, 0, nt64, _epilogue_mode())
         ctx.save_for_backward(x2d, weight)
         ctx.meta = (n, cin, h, w, kh, kw, stride, pad, cout, k, cin_k)
         stats = torch.empty(0, device=x.device)

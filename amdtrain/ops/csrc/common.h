@@ -86,13 +86,162 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
+// ---- bf16 C-tile store epilogue of the MFMA kernels -------------------------
+// (shared by gemm.hip, conv3x3.hip and conv_stem.hip)
+//
+// A wave owns a [64 rows][NF*16 cols] sub-tile as 4 x NF fragments of
+// mfma_f32_16x16x32_bf16: lane (fq = lane>>4, fr = lane&15) holds rows
+// fq*4 + r (r = 0..3) of ONE column per fragment.  Which column fragment j
+// of lane fr holds is free — it is the LDS B row that lane read — and two
+// maps are in use (epi_col):
+//   narrow: col = j*16 + fr.  One 2-byte store per element.
+//   WIDE:   col = (j>>1)*32 + (fr>>2)*8 + (j&1)*4 + (fr&3).  The 4 lanes of
+//           a quad hold 4 adjacent columns, so a 4x4 transpose inside the
+//           quad (two DPP quad_perm butterfly stages on packed bf16 pairs)
+//           leaves lane fr with row fq*4 + (fr&3), columns
+//           (fr>>2)*8 .. +7 of every 32-column group: one 16 B store per
+//           m-fragment and group, 64 contiguous bytes per row and wave
+//           instruction.  Every element is still produced by the same MFMA
+//           sequence in the same k order; only its column label moves.
+//
+// epi (runtime, AMDTRAIN_EPILOGUE): 0 = per-element predicate and 64-bit
+// row*ld+col address for every store; >= 1 = a wave whose sub-tile lies
+// fully inside [M, N] stores unpredicated through a block-uniform base and
+// 32-bit tile-local offsets (128 rows x ld x 2 B fits easily).  WIDE is a
+// compile-time variant of the kernel (it changes the K-loop's B rows),
+// needs ld % 8 == 0, and always uses the lean addressing; edge waves
+// predicate whole 16 B runs (a run never straddles N when N % 8 == 0).
+//
+// Host side every entry point takes the mode as a trailing `epi` argument;
+// a negative value selects the kernel's measured default (epi_mode).
+static inline int epi_mode(long epi, int kernel_default) {
+  return epi < 0 ? kernel_default : (int)epi;
+}
+typedef float epi_f32x4 __attribute__((ext_vector_type(4)));
+typedef float epi_f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 epi_bf16x2 __attribute__((ext_vector_type(2)));
+
+template <bool WIDE>
+__device__ __forceinline__ constexpr int epi_col(int j, int fr) {
+  return WIDE ? (j >> 1) * 32 + (fr >> 2) * 8 + (j & 1) * 4 + (fr & 3)
+              : j * 16 + fr;
+}
+
+// two fp32 -> one dword of two bf16 (lo in the low half): the same
+// round-to-nearest-even conversion as __float2bfloat16, on a real pair
+__device__ __forceinline__ unsigned epi_pack_bf16(float lo, float hi) {
+  epi_f32x2 f = {lo, hi};
+  epi_bf16x2 b = __builtin_convertvector(f, epi_bf16x2);
+  unsigned u;
+  __builtin_memcpy(&u, &b, 4);
+  return u;
+}
+
+// One m-fragment of a WIDE wave tile: a[j][r] = (row fq*4 + r, column
+// epi_col<true>(j, fr)) -> run[h] = the 8 bf16 of row fq*4 + (fr&3),
+// columns h*32 + (fr>>2)*8 .. +7.
+template <int NF>
+__device__ __forceinline__ void epi_quad_transpose(const epi_f32x4* a,
+                                                   uint4* run, int fr) {
+  const bool odd = fr & 1, low = !(fr & 2);
+  // v_perm_b32 pool: bytes 0-3 = own dword, 4-7 = the xor-1 neighbour's
+  const unsigned sel = odd ? 0x03020706u : 0x05040100u;
+  unsigned d[NF][2];
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    // rows (0,1) and (2,3) of this lane's column, packed
+    const unsigned p01 = epi_pack_bf16(a[j][0], a[j][1]);
+    const unsigned p23 = epi_pack_bf16(a[j][2], a[j][3]);
+    // stage 1, quad_perm [1,0,3,2]: even lanes collect the even row of
+    // both columns of the pair, odd lanes the odd row
+    const unsigned x01 = __builtin_amdgcn_update_dpp(0, (int)p01, 0xB1, 0xF,
+                                                     0xF, true);
+    const unsigned x23 = __builtin_amdgcn_update_dpp(0, (int)p23, 0xB1, 0xF,
+                                                     0xF, true);
+    const unsigned q01 = __builtin_amdgcn_perm(x01, p01, sel);
+    const unsigned q23 = __builtin_amdgcn_perm(x23, p23, sel);
+    // stage 2, quad_perm [2,3,0,1]: lanes 0,1 keep rows 0,1 and receive
+    // columns 2,3; lanes 2,3 keep rows 2,3 and receive columns 0,1
+    const unsigned send = low ? q23 : q01;
+    const unsigned recv = __builtin_amdgcn_update_dpp(0, (int)send, 0x4E,
+                                                      0xF, 0xF, true);
+    d[j][0] = low ? q01 : recv;
+    d[j][1] = low ? recv : q23;
+  }
+#pragma unroll
+  for (int h = 0; h < NF / 2; ++h)
+    run[h] = make_uint4(d[2 * h][0], d[2 * h][1], d[2 * h + 1][0],
+                        d[2 * h + 1][1]);
+}
+
+// Store the wave's [64][NF*16] bf16 sub-tile at rows m0 + wm.., columns
+// n0 + wn.. of C[M][N] (row pitch ld == N).  acc[i * ACCLD + j] is
+// fragment (i, j); m0 / n0 are block-uniform, wm / wn the wave's offsets.
+template <int NF, int ACCLD, bool WIDE>
+__device__ __forceinline__ void epi_store_bf16(
+    __hip_bfloat16* __restrict__ C, long ld, long m0, long M, long n0,
+    long N, int wm, int wn, int fr, int fq, const epi_f32x4* acc, int epi) {
+  const bool inside = __builtin_amdgcn_readfirstlane(
+      (int)(m0 + wm + 64 <= M && n0 + wn + NF * 16 <= N));
+  char* const blk = (char*)(C + m0 * ld + n0);
+  const unsigned ld2 = (unsigned)ld * 2;  // row pitch in bytes
+  if constexpr (WIDE) {
+    const unsigned lrow = wm + fq * 4 + (fr & 3), lcol = wn + (fr >> 2) * 8;
+    const unsigned off = lrow * ld2 + lcol * 2;
+    auto rows = [&](auto pred) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        uint4 run[NF / 2];
+        epi_quad_transpose<NF>(acc + i * ACCLD, run, fr);
+        if (!pred.value || m0 + lrow + i * 16 < M) {
+#pragma unroll
+          for (int h = 0; h < NF / 2; ++h)
+            if (!pred.value || n0 + lcol + h * 32 + 8 <= N)
+              *(uint4*)(blk + (off + i * 16 * ld2 + h * 64)) = run[h];
+        }
+      }
+    };
+    if (inside)
+      rows(std::false_type{});
+    else
+      rows(std::true_type{});
+    return;
+  }
+  if (inside && epi >= 1) {
+    const unsigned off = (wm + fq * 4) * ld2 + (wn + fr) * 2;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned roff = off + (i * 16 + r) * ld2;
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+          *(__hip_bfloat16*)(blk + (roff + j * 32)) =
+              __float2bfloat16(acc[i * ACCLD + j][r]);
+      }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        long row = m0 + wm + i * 16 + fq * 4 + r;
+        long col = n0 + wn + j * 16 + fr;
+        if (row < M && col < N)
+          C[row * ld + col] = __float2bfloat16(acc[i * ACCLD + j][r]);
+      }
+}
+
 // ---- implicit-GEMM conv epilogue: BN-statistics partials --------------------
 // (shared by conv3x3.hip and conv_stem.hip)
 // per-block column (sum, sumsq) of the fp32 accumulator tile (see
 // gemm.hip) of a 128-row block whose 4 waves form a 2m x 2n grid of
 // 4 x (NTE/32) 16x16 fragments; NTE = n-tile width (128 or 64).  Writes row
 // bm of stats [nbm][2*N]; lds_scratch needs 4*NTE floats.
-template <int NTE = 128>
+// WIDE: the kernel's column map (epi_col) — only the column label moves.
+template <int NTE = 128, bool WIDE = false>
 __device__ __forceinline__ void conv_epilogue_stats(
     float* __restrict__ stats, const float* acc_flat, long m0, long M,
     long n0, long N, int bm, int wm, int wn, int fr, int fq,
@@ -127,7 +276,7 @@ __device__ __forceinline__ void conv_epilogue_stats(
   if (fq == 0) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-      int col = wn + j * 16 + fr;
+      int col = wn + epi_col<WIDE>(j, fr);
       red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 0] = s1[j];
       red[(wm ? 1 : 0) * (2 * NTE) + col * 2 + 1] = s2[j];
     }

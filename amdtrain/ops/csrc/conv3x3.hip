@@ -217,13 +217,16 @@ __device__ __forceinline__ void stage_plain(
 // loop in the same order.  M is the TOTAL row count (4 classes of M/4),
 // nbm = 4 * tiles-per-class; the class is the fastest block index so the
 // 1/2/2/4-tap blocks interleave evenly over the XCDs.
+// WIDE: the wide-store C epilogue and its B-row map (common.h); epi is the
+// runtime mode of the narrow one (AMDTRAIN_EPILOGUE 0 / 1; PAR rows are
+// not affine in the tile row, so the narrow PAR store has one form only).
 template <bool DGRAD, int BKT = BK, bool BAND = false, int NT = 128,
-          bool DB = false, bool PAR = false>
+          bool DB = false, bool PAR = false, bool WIDE = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
                bf16* __restrict__ C, long M, int AC, int NC, ConvGeom g,
                int nbm, int nbn, const bf16* __restrict__ zero_page,
-               float* __restrict__ stats) {
+               float* __restrict__ stats, int epi) {
   static_assert(!PAR || (DGRAD && !BAND), "PAR is a dense-dgrad variant");
   constexpr int STG = (128 + NT) * BKT;  // one A+B stage
   __shared__ bf16 SMEM[(DB ? 2 : 1) * STG];
@@ -291,7 +294,7 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
 #pragma unroll
       for (int j = 0; j < NFR; ++j)
         b[j] = *(const bf16x8*)
-            &bs[(wn + j * 16 + fr) * BKT + kk * 32 + fq * 8];
+            &bs[(wn + epi_col<WIDE>(j, fr)) * BKT + kk * 32 + fq * 8];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -319,6 +322,29 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     }
   }
 
+  if (PAR && WIDE) {
+    // after the quad transpose a lane holds ONE class row per m-fragment:
+    // decode it to the true input row and store its 16 B runs
+    const unsigned W2 = g.W >> 1, H2 = g.H >> 1;
+    const long lcol = n0 + wn + (fr >> 2) * 8;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      uint4 run[NFR / 2];
+      epi_quad_transpose<NFR>(&acc[i][0], run, fr);
+      const unsigned mr = (unsigned)m0 + wm + i * 16 + fq * 4 + (fr & 3);
+      if ((long)mr < Mr) {
+        const unsigned w2 = mr % W2, t2 = mr / W2;
+        const unsigned h2 = t2 % H2, n = t2 / H2;
+        const long row = ((long)n * g.H + 2 * h2 + par_h) * g.W + 2 * w2 +
+                         par_w;
+#pragma unroll
+        for (int h = 0; h < NFR / 2; ++h)
+          if (lcol + h * 32 + 8 <= NC)
+            *(uint4*)(C + row * NC + lcol + h * 32) = run[h];
+      }
+    }
+    return;
+  }
   if (PAR) {
     // class row -> true input row; one decode per 4-row fragment group,
     // then step (w2, h2, n) with carries (host guarantees M < 2^31)
@@ -351,20 +377,11 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     }
     return;
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NFR; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long row = m0 + wm + i * 16 + fq * 4 + r;
-        long col = n0 + wn + j * 16 + fr;
-        if (row < M && col < NC)
-          C[row * NC + col] = __float2bfloat16(acc[i][j][r]);
-      }
+  epi_store_bf16<NFR, NFR, WIDE>(C, NC, m0, M, n0, NC, wm, wn, fr, fq,
+                                 &acc[0][0], epi);
   if (stats != nullptr)
-    conv_epilogue_stats<NT>(stats, (const float*)acc, m0, M, n0, NC, bm,
-                            wm, wn, fr, fq, As);
+    conv_epilogue_stats<NT, WIDE>(stats, (const float*)acc, m0, M, n0, NC,
+                                  bm, wm, wn, fr, fq, As);
 }
 
 // wgrad per tap: dW[cout, tap*Cin + cin] += sum_m dY[m, cout] * Xg[m, cin]
@@ -506,12 +523,33 @@ static at::Tensor zero_page_for(const at::Tensor& like) {
   return zp;
 }
 
+// one conv3x3_kernel launch; the double-buffered dense variants also exist
+// with the wide-store epilogue (wide: AMDTRAIN_EPILOGUE=2 and NC % 8 == 0)
+template <bool DGRAD, int BKT, bool BAND, int NT, bool DB, bool PAR = false>
+static void launch_c3(bool wide, int grid, hipStream_t stream, const bf16* A,
+                      const bf16* Bw, bf16* C, long M, int AC, int NC,
+                      const ConvGeom& g, int nbm, int nbn, const bf16* zp,
+                      float* stats, int epi) {
+  if constexpr (DB && !BAND) {
+    if (wide) {
+      conv3x3_kernel<DGRAD, BKT, BAND, NT, DB, PAR, true>
+          <<<grid, GEMM_TPB, 0, stream>>>(A, Bw, C, M, AC, NC, g, nbm, nbn,
+                                          zp, stats, epi);
+      return;
+    }
+  }
+  conv3x3_kernel<DGRAD, BKT, BAND, NT, DB, PAR, false>
+      <<<grid, GEMM_TPB, 0, stream>>>(A, Bw, C, M, AC, NC, g, nbm, nbn, zp,
+                                      stats, epi);
+}
+
 std::vector<at::Tensor> conv3x3_fwd_stats_impl(at::Tensor x2d, long Nn,
                                                 long H, long W, long stride,
                                                 at::Tensor w2d,
                                                 bool want_stats,
                                                 bool banded = false,
-                                                bool nt64 = true) {
+                                                bool nt64 = true,
+                                                long epi = -1) {
   // x2d: [Nn*H*W, Cin] bf16 NHWC rows; w2d: [Cout, 9*Cin]
   TORCH_CHECK(x2d.is_cuda() && x2d.scalar_type() == at::kBFloat16);
   long Cin = x2d.size(1), Cout = w2d.size(0);
@@ -524,93 +562,81 @@ std::vector<at::Tensor> conv3x3_fwd_stats_impl(at::Tensor x2d, long Nn,
   int nbm = (int)((M + 127) / 128), nbn = (int)((Cout + 127) / 128);
   auto zp = zero_page_for(x2d);
   at::Tensor stats;
-  float* stats_ptr = nullptr;
+  float* sp = nullptr;
   if (want_stats) {
     stats = at::empty({nbm, 2 * Cout}, x2d.options().dtype(at::kFloat));
-    stats_ptr = stats.data_ptr<float>();
+    sp = stats.data_ptr<float>();
   }
   auto stream = at::cuda::getCurrentCUDAStream();
   static const bool bk64 = []() {
     const char* v = std::getenv("AMDTRAIN_CONV3X3_BK64");
     return !(v && v[0] == '0');
   }();
+  const bf16* xp = (const bf16*)x2d.const_data_ptr();
+  const bf16* wp = (const bf16*)w2d.const_data_ptr();
+  const bf16* zpp = (const bf16*)zp.const_data_ptr();
+  bf16* yp = (bf16*)y.data_ptr();
+  const int ci = (int)Cin, co = (int)Cout, ep = epi_mode(epi, 2);
+  const bool wide = ep >= 2 && Cout % 8 == 0;
+  const bool db = conv3x3_db_enabled();
   // A/B (tools/bench_conv3x3.py + in-context traces): BK64 fwd +17% at
   // layer2 (Cin=128, M=400k); layer1 (Cin=64) and layer3/4 (small M)
   // measured WORSE in-context -> Cin>=128 && large-M only
   if (banded) {  // requires Cin == Cout, both % 128 (host-checked)
     // NT=64 tile halves the group-band window (and the off-diag waste)
     int nbn64 = (int)((Cout + 63) / 64);
-    if (conv3x3_db_enabled())
-      conv3x3_kernel<false, BK, true, 64, true>
-          <<<nbm * nbn64, GEMM_TPB, 0, stream>>>(
-              (const bf16*)x2d.const_data_ptr(),
-              (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-              (int)Cin, (int)Cout, g, nbm, nbn64,
-              (const bf16*)zp.const_data_ptr(), stats_ptr);
+    if (db)
+      launch_c3<false, BK, true, 64, true>(wide, nbm * nbn64, stream, xp, wp,
+                                           yp, M, ci, co, g, nbm, nbn64, zpp,
+                                           sp, ep);
     else
-      conv3x3_kernel<false, BK, true, 64>
-          <<<nbm * nbn64, GEMM_TPB, 0, stream>>>(
-              (const bf16*)x2d.const_data_ptr(),
-              (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-              (int)Cin, (int)Cout, g, nbm, nbn64,
-              (const bf16*)zp.const_data_ptr(), stats_ptr);
-  } else if (nt64 && Cout <= 64 && conv3x3_db_enabled()) {
+      launch_c3<false, BK, true, 64, false>(wide, nbm * nbn64, stream, xp,
+                                            wp, yp, M, ci, co, g, nbm, nbn64,
+                                            zpp, sp, ep);
+  } else if (nt64 && Cout <= 64 && db) {
     // narrow output (layer 1): the 64-wide n-tile issues no MFMAs on the
     // clamped B rows 64..127 of the 128-wide tile; per-element K order
     // and per-block row sets are unchanged, so y and the stats partials
     // equal the 128-wide tile's
-    conv3x3_kernel<false, BK, false, 64, true>
-        <<<nbm, GEMM_TPB, 0, stream>>>(
-            (const bf16*)x2d.const_data_ptr(),
-            (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-            (int)Cin, (int)Cout, g, nbm, 1,
-            (const bf16*)zp.const_data_ptr(), stats_ptr);
+    launch_c3<false, BK, false, 64, true>(wide, nbm, stream, xp, wp, yp, M,
+                                          ci, co, g, nbm, 1, zpp, sp, ep);
   } else if (bk64 && Cin % 64 == 0 && Cin >= 128 && M >= 200000) {
-    if (conv3x3_db_enabled())
-      conv3x3_kernel<false, 64, false, 128, true>
-          <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-              (const bf16*)x2d.const_data_ptr(),
-              (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-              (int)Cin, (int)Cout, g, nbm, nbn,
-              (const bf16*)zp.const_data_ptr(), stats_ptr);
+    if (db)
+      launch_c3<false, 64, false, 128, true>(wide, nbm * nbn, stream, xp, wp,
+                                             yp, M, ci, co, g, nbm, nbn, zpp,
+                                             sp, ep);
     else
-      conv3x3_kernel<false, 64><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-          (const bf16*)x2d.const_data_ptr(),
-          (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-          (int)Cin, (int)Cout, g, nbm, nbn,
-          (const bf16*)zp.const_data_ptr(), stats_ptr);
-  } else if (conv3x3_db_enabled())
-    conv3x3_kernel<false, BK, false, 128, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)x2d.const_data_ptr(),
-            (const bf16*)w2d.const_data_ptr(), (bf16*)y.data_ptr(), M,
-            (int)Cin, (int)Cout, g, nbm, nbn,
-            (const bf16*)zp.const_data_ptr(), stats_ptr);
+      launch_c3<false, 64, false, 128, false>(wide, nbm * nbn, stream, xp,
+                                              wp, yp, M, ci, co, g, nbm, nbn,
+                                              zpp, sp, ep);
+  } else if (db)
+    launch_c3<false, BK, false, 128, true>(wide, nbm * nbn, stream, xp, wp,
+                                           yp, M, ci, co, g, nbm, nbn, zpp,
+                                           sp, ep);
   else
-    conv3x3_kernel<false><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)x2d.const_data_ptr(), (const bf16*)w2d.const_data_ptr(),
-        (bf16*)y.data_ptr(), M, (int)Cin, (int)Cout, g, nbm, nbn,
-        (const bf16*)zp.const_data_ptr(), stats_ptr);
+    launch_c3<false, BK, false, 128, false>(wide, nbm * nbn, stream, xp, wp,
+                                            yp, M, ci, co, g, nbm, nbn, zpp,
+                                            sp, ep);
   CHECK_CUDA_OK();
   if (want_stats) return {y, stats};
   return {y};
 }
 
 at::Tensor conv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
-                       at::Tensor w2d, bool nt64) {
+                       at::Tensor w2d, bool nt64, long epi) {
   return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, false, false,
-                                nt64)[0];
+                                nt64, epi)[0];
 }
 
 std::vector<at::Tensor> conv3x3_fwd_stats(at::Tensor x2d, long Nn, long H,
                                           long W, long stride,
                                           at::Tensor w2d, bool banded,
-                                          bool nt64) {
+                                          bool nt64, long epi) {
   TORCH_CHECK(!banded || (x2d.size(1) == w2d.size(0) &&
                           x2d.size(1) % 128 == 0),
               "banded conv3x3 needs Cin == Cout, both % 128");
   return conv3x3_fwd_stats_impl(x2d, Nn, H, W, stride, w2d, true, banded,
-                                nt64);
+                                nt64, epi);
 }
 
 // s2parity: stride-2 calls with even H and W run the parity-class tiling
@@ -619,7 +645,7 @@ std::vector<at::Tensor> conv3x3_fwd_stats(at::Tensor x2d, long Nn, long H,
 // double-buffered pipeline (AMDTRAIN_CONV3X3_DB=0 keeps the old loop).
 at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
                          long stride, at::Tensor w2d, bool banded,
-                         bool s2parity, bool nt64) {
+                         bool s2parity, bool nt64, long epi) {
   // dy2d: [Nn*Hout*Wout, Cout]; returns dx2d [Nn*H*W, Cin]
   long Cout = dy2d.size(1), Cin = w2d.size(1) / 9;
   TORCH_CHECK(w2d.size(0) == Cout && w2d.size(1) == 9 * Cin);
@@ -637,25 +663,26 @@ at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
   ConvGeom g{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride};
   int nbm = (int)((M + 127) / 128), nbn = (int)((Cin + 127) / 128);
   auto zp = zero_page_for(dy2d);
+  const bf16* yp = (const bf16*)dy2d.const_data_ptr();
+  const bf16* wp = (const bf16*)wrot.const_data_ptr();
+  const bf16* zpp = (const bf16*)zp.const_data_ptr();
+  bf16* xp = (bf16*)dx.data_ptr();
+  const int ci = (int)Cin, co = (int)Cout, ep = epi_mode(epi, 2);
+  const bool wide = ep >= 2 && Cin % 8 == 0;
+  const bool db = conv3x3_db_enabled();
   if (banded) {
     TORCH_CHECK(Cin == Cout && Cin % 128 == 0);
     // NT=64 tile: the group-diagonal K window shrinks to 64 channels,
     // halving the off-diagonal waste vs the 128-wide tile
     int nbn64 = (int)(Cin / 64);
-    if (conv3x3_db_enabled())
-      conv3x3_kernel<true, BK, true, 64, true>
-          <<<nbm * nbn64, GEMM_TPB, 0, stream>>>(
-              (const bf16*)dy2d.const_data_ptr(),
-              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-              (int)Cout, (int)Cin, g, nbm, nbn64,
-              (const bf16*)zp.const_data_ptr(), nullptr);
+    if (db)
+      launch_c3<true, BK, true, 64, true>(wide, nbm * nbn64, stream, yp, wp,
+                                          xp, M, co, ci, g, nbm, nbn64, zpp,
+                                          nullptr, ep);
     else
-      conv3x3_kernel<true, BK, true, 64>
-          <<<nbm * nbn64, GEMM_TPB, 0, stream>>>(
-              (const bf16*)dy2d.const_data_ptr(),
-              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-              (int)Cout, (int)Cin, g, nbm, nbn64,
-              (const bf16*)zp.const_data_ptr(), nullptr);
+      launch_c3<true, BK, true, 64, false>(wide, nbm * nbn64, stream, yp, wp,
+                                           xp, M, co, ci, g, nbm, nbn64, zpp,
+                                           nullptr, ep);
     CHECK_CUDA_OK();
     return dx;
   }
@@ -664,51 +691,36 @@ at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
     return v && v[0] == '1';
   }();
   const bool par = s2parity && stride == 2 && H % 2 == 0 && W % 2 == 0 &&
-                   M < (1L << 31) && conv3x3_db_enabled();
-  const bool n64 = nt64 && Cin <= 64 && conv3x3_db_enabled();
+                   M < (1L << 31) && db;
+  const bool n64 = nt64 && Cin <= 64 && db;
   if (par) {
     // four parity classes of M/4 rows, each tiled on its own
     const int nbmp = 4 * (int)((M / 4 + 127) / 128);
     if (n64)
-      conv3x3_kernel<true, BK, false, 64, true, true>
-          <<<nbmp, GEMM_TPB, 0, stream>>>(
-              (const bf16*)dy2d.const_data_ptr(),
-              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-              (int)Cout, (int)Cin, g, nbmp, 1,
-              (const bf16*)zp.const_data_ptr(), nullptr);
+      launch_c3<true, BK, false, 64, true, true>(wide, nbmp, stream, yp, wp,
+                                                 xp, M, co, ci, g, nbmp, 1,
+                                                 zpp, nullptr, ep);
     else
-      conv3x3_kernel<true, BK, false, 128, true, true>
-          <<<nbmp * nbn, GEMM_TPB, 0, stream>>>(
-              (const bf16*)dy2d.const_data_ptr(),
-              (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-              (int)Cout, (int)Cin, g, nbmp, nbn,
-              (const bf16*)zp.const_data_ptr(), nullptr);
+      launch_c3<true, BK, false, 128, true, true>(wide, nbmp * nbn, stream,
+                                                  yp, wp, xp, M, co, ci, g,
+                                                  nbmp, nbn, zpp, nullptr,
+                                                  ep);
   } else if (n64)
-    conv3x3_kernel<true, BK, false, 64, true>
-        <<<nbm, GEMM_TPB, 0, stream>>>(
-            (const bf16*)dy2d.const_data_ptr(),
-            (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-            (int)Cout, (int)Cin, g, nbm, 1,
-            (const bf16*)zp.const_data_ptr(), nullptr);
+    launch_c3<true, BK, false, 64, true>(wide, nbm, stream, yp, wp, xp, M,
+                                         co, ci, g, nbm, 1, zpp, nullptr,
+                                         ep);
   else if (bk64d && Cout % 64 == 0)
-    conv3x3_kernel<true, 64><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)dy2d.const_data_ptr(),
-        (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-        (int)Cout, (int)Cin, g, nbm, nbn,
-        (const bf16*)zp.const_data_ptr(), nullptr);
-  else if (conv3x3_db_enabled())
-    conv3x3_kernel<true, BK, false, 128, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)dy2d.const_data_ptr(),
-            (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-            (int)Cout, (int)Cin, g, nbm, nbn,
-            (const bf16*)zp.const_data_ptr(), nullptr);
+    launch_c3<true, 64, false, 128, false>(wide, nbm * nbn, stream, yp, wp,
+                                           xp, M, co, ci, g, nbm, nbn, zpp,
+                                           nullptr, ep);
+  else if (db)
+    launch_c3<true, BK, false, 128, true>(wide, nbm * nbn, stream, yp, wp,
+                                          xp, M, co, ci, g, nbm, nbn, zpp,
+                                          nullptr, ep);
   else
-    conv3x3_kernel<true><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)dy2d.const_data_ptr(),
-        (const bf16*)wrot.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-        (int)Cout, (int)Cin, g, nbm, nbn,
-        (const bf16*)zp.const_data_ptr(), nullptr);
+    launch_c3<true, BK, false, 128, false>(wide, nbm * nbn, stream, yp, wp,
+                                           xp, M, co, ci, g, nbm, nbn, zpp,
+                                           nullptr, ep);
   CHECK_CUDA_OK();
   return dx;
 }

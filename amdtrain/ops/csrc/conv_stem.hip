@@ -222,14 +222,16 @@ __device__ __forceinline__ void stage_row4(
 // from the fp32 accumulator (conv_epilogue_stats).
 // DB: double-buffered K-loop (gemm.hip pattern — stage ks+1's tiles while
 // ks computes, one barrier per chunk), AMDTRAIN_STEM_DB=0 reverts.
+// WIDE: the wide-store C epilogue and its B-row map (common.h); epi is the
+// runtime mode of the narrow one (AMDTRAIN_EPILOGUE 0 / 1).
 template <bool DGRAD = false, bool C8 = false, bool DB = false, int NT = 128,
-          bool ROW4 = false>
+          bool ROW4 = false, bool WIDE = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 conv_generic_fwd_kernel(const bf16* __restrict__ x,
                         const bf16* __restrict__ W2, bf16* __restrict__ Y,
                         long M, int Cout, StemGeom g, int nbm, int nbn,
                         const bf16* __restrict__ zp,
-                        float* __restrict__ stats) {
+                        float* __restrict__ stats, int epi) {
   static_assert(!ROW4 || (C8 && !DGRAD), "ROW4 is a C8 forward staging");
   constexpr int STG = (128 + NT) * BK;  // one A+B stage
   constexpr int NFR = NT / 32;          // n fragments per wave
@@ -286,7 +288,8 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
       a[i] = *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
 #pragma unroll
     for (int j = 0; j < NFR; ++j)
-      b[j] = *(const bf16x8*)&bs[(wn + j * 16 + fr) * BK + fq * 8];
+      b[j] = *(const bf16x8*)
+          &bs[(wn + epi_col<WIDE>(j, fr)) * BK + fq * 8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -311,20 +314,11 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
       compute(SMEM);
     }
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NFR; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long row = m0 + wm + i * 16 + fq * 4 + r;
-        long col = n0 + wn + j * 16 + fr;
-        if (row < M && col < Cout)
-          Y[row * Cout + col] = __float2bfloat16(acc[i][j][r]);
-      }
+  epi_store_bf16<NFR, NFR, WIDE>(Y, Cout, m0, M, n0, Cout, wm, wn, fr, fq,
+                                 &acc[0][0], epi);
   if (stats != nullptr)
-    conv_epilogue_stats<NT>(stats, (const float*)acc, m0, M, n0, Cout, bm,
-                            wm, wn, fr, fq, SMEM);
+    conv_epilogue_stats<NT, WIDE>(stats, (const float*)acc, m0, M, n0, Cout,
+                                  bm, wm, wn, fr, fq, SMEM);
 }
 
 // wgrad: transposed reg-staging like gemm.hip's gemm_tn, with the B chunk
@@ -460,14 +454,24 @@ static StemGeom make_geom(long H, long W, long KH, long KW, long Cin,
   return g;
 }
 
+// the double-buffered C8 forward variants (the stem) also exist with the
+// wide-store epilogue (wide: AMDTRAIN_EPILOGUE=2 and Cout % 8 == 0)
 template <bool DGRAD, bool C8, bool DBUF, int NT = 128, bool ROW4 = false>
 static void stem_launch(int grid, hipStream_t stream, const bf16* x,
                         const bf16* w2, bf16* y, long M, int Cout,
                         const StemGeom& g, int nbm, int nbn, const bf16* zp,
-                        float* stats) {
-  conv_generic_fwd_kernel<DGRAD, C8, DBUF, NT, ROW4>
+                        float* stats, bool wide, int epi) {
+  if constexpr (C8 && DBUF && !DGRAD) {
+    if (wide) {
+      conv_generic_fwd_kernel<DGRAD, C8, DBUF, NT, ROW4, true>
+          <<<grid, GEMM_TPB, 0, stream>>>(x, w2, y, M, Cout, g, nbm, nbn, zp,
+                                          stats, epi);
+      return;
+    }
+  }
+  conv_generic_fwd_kernel<DGRAD, C8, DBUF, NT, ROW4, false>
       <<<grid, GEMM_TPB, 0, stream>>>(x, w2, y, M, Cout, g, nbm, nbn, zp,
-                                      stats);
+                                      stats, epi);
 }
 
 static at::Tensor stem_zero_page(const at::Tensor& like) {
@@ -499,7 +503,7 @@ static bool stem_db_enabled() {
 static std::vector<at::Tensor> conv_generic_fwd_impl(
     at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
     long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
-    bool want_stats, bool tile64) {
+    bool want_stats, bool tile64, long epi) {
   TORCH_CHECK(x2d.is_cuda() && x2d.scalar_type() == at::kBFloat16);
   TORCH_CHECK(x2d.is_contiguous() && w2.is_contiguous());
   long Cin = x2d.size(1), Cout = w2.size(0);
@@ -527,31 +531,32 @@ static std::vector<at::Tensor> conv_generic_fwd_impl(
   const bf16* wp = (const bf16*)w2.const_data_ptr();
   const bf16* zpp = (const bf16*)zp.const_data_ptr();
   bf16* yp = (bf16*)y.data_ptr();
-  const int grid = nbm * nbn, co = (int)Cout;
+  const int grid = nbm * nbn, co = (int)Cout, ep = epi_mode(epi, 2);
+  const bool wide = ep >= 2 && Cout % 8 == 0;
   if (c8 && row4 && t64 && db)
     stem_launch<false, true, true, 64, true>(grid, stream, xp, wp, yp, M, co,
-                                             g, nbm, nbn, zpp, sp);
+                                             g, nbm, nbn, zpp, sp, wide, ep);
   else if (c8 && row4 && t64)
     stem_launch<false, true, false, 64, true>(grid, stream, xp, wp, yp, M, co,
-                                              g, nbm, nbn, zpp, sp);
+                                              g, nbm, nbn, zpp, sp, wide, ep);
   else if (c8 && t64 && db)  // 49-tap stem: same K order, half the MFMAs
     stem_launch<false, true, true, 64>(grid, stream, xp, wp, yp, M, co, g,
-                                       nbm, nbn, zpp, sp);
+                                       nbm, nbn, zpp, sp, wide, ep);
   else if (c8 && t64)
     stem_launch<false, true, false, 64>(grid, stream, xp, wp, yp, M, co, g,
-                                        nbm, nbn, zpp, sp);
+                                        nbm, nbn, zpp, sp, wide, ep);
   else if (c8 && db)
     stem_launch<false, true, true>(grid, stream, xp, wp, yp, M, co, g, nbm,
-                                   nbn, zpp, sp);
+                                   nbn, zpp, sp, wide, ep);
   else if (c8)
     stem_launch<false, true, false>(grid, stream, xp, wp, yp, M, co, g, nbm,
-                                    nbn, zpp, sp);
+                                    nbn, zpp, sp, wide, ep);
   else if (db)
     stem_launch<false, false, true>(grid, stream, xp, wp, yp, M, co, g, nbm,
-                                    nbn, zpp, sp);
+                                    nbn, zpp, sp, wide, ep);
   else
     stem_launch<false, false, false>(grid, stream, xp, wp, yp, M, co, g, nbm,
-                                     nbn, zpp, sp);
+                                     nbn, zpp, sp, wide, ep);
   CHECK_CUDA_OK();
   if (want_stats) return {y, stats};
   return {y};
@@ -560,17 +565,19 @@ static std::vector<at::Tensor> conv_generic_fwd_impl(
 at::Tensor conv_generic_fwd(at::Tensor x2d, long Nn, long H, long W,
                             long KH, long KW, long stride, long pad,
                             at::Tensor w2, long stride_w, long pad_w,
-                            long Hout, long Wout, bool tile64) {
+                            long Hout, long Wout, bool tile64, long epi) {
   return conv_generic_fwd_impl(x2d, Nn, H, W, KH, KW, stride, pad, w2,
-                               stride_w, pad_w, Hout, Wout, false, tile64)[0];
+                               stride_w, pad_w, Hout, Wout, false, tile64,
+                               epi)[0];
 }
 
 std::vector<at::Tensor> conv_generic_fwd_stats(
     at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
     long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
-    bool tile64) {
+    bool tile64, long epi) {
   return conv_generic_fwd_impl(x2d, Nn, H, W, KH, KW, stride, pad, w2,
-                               stride_w, pad_w, Hout, Wout, true, tile64);
+                               stride_w, pad_w, Hout, Wout, true, tile64,
+                               epi);
 }
 
 // dy2d: [N*Hout*Wout, Cout]; w2p: [Cin, pad32(KH*KW*Cout)] (weight permuted
@@ -595,12 +602,13 @@ at::Tensor conv_generic_dgrad(at::Tensor dy2d, at::Tensor w2p, long Nn,
             (const bf16*)dy2d.const_data_ptr(),
             (const bf16*)w2p.const_data_ptr(), (bf16*)dx.data_ptr(), M,
             (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr(),
-            nullptr);
+            nullptr, 0);
   else
     conv_generic_fwd_kernel<true><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
         (const bf16*)dy2d.const_data_ptr(),
         (const bf16*)w2p.const_data_ptr(), (bf16*)dx.data_ptr(), M,
-        (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr(), nullptr);
+        (int)Cin, g, nbm, nbn, (const bf16*)zp.const_data_ptr(), nullptr,
+        0);
   CHECK_CUDA_OK();
   return dx;
 }

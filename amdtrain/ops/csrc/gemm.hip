@@ -128,7 +128,8 @@ __device__ __forceinline__ long stride_row(long m, const StrideMap& sm) {
 // per-block column (sum, sumsq) of the fp32 accumulator tile -> one row of
 // stats[bm][2N]: feeds BN forward without re-reading the conv output.
 // acc layout: lane holds col = base+fr, rows (i*16 + fq*4 + r).
-template <int NFRAG>
+// WIDE: the kernel's column map (common.h epi_col) — only the label moves.
+template <int NFRAG, bool WIDE = false>
 __device__ __forceinline__ void epilogue_stats(
     float* __restrict__ stats, const float* acc_flat, long m0, long M,
     long n0, long N, int bm, int wm, int wn, int fr, int fq, int nbm,
@@ -166,7 +167,7 @@ __device__ __forceinline__ void epilogue_stats(
   if (fq == 0) {
 #pragma unroll
     for (int j = 0; j < NFRAG; ++j) {
-      int col = wn + j * 16 + fr;
+      int col = wn + epi_col<WIDE>(j, fr);
       red[(wm ? 1 : 0) * 256 + col * 2 + 0] = s1[j];
       red[(wm ? 1 : 0) * 256 + col * 2 + 1] = s2[j];
     }
@@ -199,12 +200,15 @@ __device__ __forceinline__ void epilogue_stats(
 // A-side DMA and half the LDS footprint disappear; the second wave on
 // the same rows hits L1.  A/B experiment for the streaming shapes
 // (AMDTRAIN_GEMM_ADIR).  Plain (non-strided, non-LDSE) path only.
+// WIDE: the wide-store C epilogue and its B-row map (common.h); epi is the
+// runtime epilogue mode of the narrow one (AMDTRAIN_EPILOGUE 0 / 1).
 template <bool F32OUT, bool STRIDED, bool NT = false, bool LDSE = false,
-          bool DB = false, bool ADIR = false>
+          bool DB = false, bool ADIR = false, bool WIDE = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                void* __restrict__ C, long M, long N, long K, int nbm,
-               int nbn, StrideMap sm, float* __restrict__ stats) {
+               int nbn, StrideMap sm, float* __restrict__ stats, int epi) {
+  static_assert(!WIDE || !(F32OUT || NT || LDSE), "WIDE is a bf16 epilogue");
   __shared__ bf16 SMEM[(DB ? 2 : 1) *
                        ((ADIR ? 0 : BM) + BN) * BK];  // [As |] Bs
   bf16* const As = SMEM;    // (contiguous: the LDSE epilogue reuses 16 KB)
@@ -269,7 +273,8 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                   : *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      b[j] = *(const bf16x8*)&bs[(wn + j * 16 + fr) * BK + fq * 8];
+      b[j] = *(const bf16x8*)
+          &bs[(wn + epi_col<WIDE>(j, fr)) * BK + fq * 8];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -324,7 +329,7 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
               ((const uint4*)SMEM)[u2];
       }
     }
-  } else {
+  } else if (F32OUT || NT) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -336,22 +341,23 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
           if (row < M && col < N) {
             if (F32OUT) {
               ((float*)C)[row * N + col] = acc[i][j][r];
-            } else if (NT) {
+            } else {
               bf16 v = __float2bfloat16(acc[i][j][r]);
               short b;
               __builtin_memcpy(&b, &v, 2);
               __builtin_nontemporal_store(b, (short*)C + row * N + col);
-            } else {
-              ((bf16*)C)[row * N + col] = __float2bfloat16(acc[i][j][r]);
             }
           }
         }
       }
     }
+  } else {
+    epi_store_bf16<4, 4, WIDE>((bf16*)C, N, m0, M, n0, N, wm, wn, fr, fq,
+                               &acc[0][0], epi);
   }
   if (stats != nullptr)
-    epilogue_stats<4>(stats, (const float*)acc, m0, M, n0, N, bm, wm, wn,
-                      fr, fq, nbm, As);
+    epilogue_stats<4, WIDE>(stats, (const float*)acc, m0, M, n0, N, bm, wm,
+                            wn, fr, fq, nbm, As);
 }
 
 // ---- dual-N-tile BT GEMM (A-panel reuse) ---------------------------------
@@ -362,11 +368,12 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
 // uniform streaming-efficiency wall, not the A re-reads — the rr-floor
 // coincidence in the first analysis was misleading); kept because it also
 // halves launch width and is covered by tests.
-template <bool DB = false>
+template <bool DB = false, bool WIDE = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 gemm_bt_n2_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                   bf16* __restrict__ C, long M, long N, long K, int nbm,
-                  int nbn2, float* __restrict__ stats, int nbm_stats) {
+                  int nbn2, float* __restrict__ stats, int nbm_stats,
+                  int epi) {
   __shared__ bf16 SMEM[(DB ? 2 : 1) * (BM + 256) * BK];
   bf16* const As = SMEM;
   bf16* const Bs = SMEM + BM * BK;
@@ -404,8 +411,8 @@ gemm_bt_n2_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
       a[i] = *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int jn = (j < 4) ? wn + j * 16 : 128 + wn + (j - 4) * 16;
-      b[j] = *(const bf16x8*)&bs[(jn + fr) * BK + fq * 8];
+      const int jn = (j < 4 ? 0 : 128) + wn + epi_col<WIDE>(j & 3, fr);
+      b[j] = *(const bf16x8*)&bs[jn * BK + fq * 8];
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -432,18 +439,11 @@ gemm_bt_n2_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
     }
   }
 
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long row = m0 + wm + i * 16 + fq * 4 + r;
-        long col = n0 + ((j < 4) ? wn + j * 16 : 128 + wn + (j - 4) * 16)
-                   + fr;
-        if (row < M && col < N)
-          C[row * N + col] = __float2bfloat16(acc[i][j][r]);
-      }
+  // the two 128-column halves, each a [64][64] wave tile (N % 256 == 0)
+  epi_store_bf16<4, 8, WIDE>(C, N, m0, M, n0, N, wm, wn, fr, fq,
+                             &acc[0][0], epi);
+  epi_store_bf16<4, 8, WIDE>(C, N, m0, M, n0, N, wm, 128 + wn, fr, fq,
+                             &acc[0][4], epi);
   if (stats != nullptr) {
     // per-block column (sum, sumsq) partials for the fused BN pipeline —
     // two 128-col halves through the shared epilogue helper
@@ -457,11 +457,11 @@ gemm_bt_n2_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
           accl[i][j][r] = acc[i][j][r];
           acch[i][j][r] = acc[i][j + 4][r];
         }
-    epilogue_stats<4>(stats, (const float*)accl, m0, M, n0, N, bm, wm, wn,
-                      fr, fq, nbm_stats, As);
+    epilogue_stats<4, WIDE>(stats, (const float*)accl, m0, M, n0, N, bm, wm,
+                            wn, fr, fq, nbm_stats, As);
     __syncthreads();
-    epilogue_stats<4>(stats, (const float*)acch, m0, M, n0 + 128, N, bm,
-                      wm, wn, fr, fq, nbm_stats, As);
+    epilogue_stats<4, WIDE>(stats, (const float*)acch, m0, M, n0 + 128, N,
+                            bm, wm, wn, fr, fq, nbm_stats, As);
   }
 }
 
@@ -715,9 +715,53 @@ transpose_2d_kernel(const bf16* __restrict__ in, bf16* __restrict__ out,
 
 }  // namespace
 
+// epi: AMDTRAIN_EPILOGUE mode of the bf16 C store (common.h) — 0 the
+// per-element predicated store, 1 lean addressing on interior tiles, 2 lean
+// addressing + 16 B stores (needs N % 8 == 0; other N run mode 1).  The
+// mode is an argument, not a process-wide static, so one process can
+// compare the paths.  Measured defaults (profiles/README.md): 2 for
+// gemm_bt_kernel; 1 for the dual-n-tile kernel, whose write-dominated
+// shapes gain 10-27 % from the lean addressing and lose most of that again
+// with the 16 B stores.
+constexpr int EPI_DEFAULT_BT = 2, EPI_DEFAULT_N2 = 1;
+static inline bool epi_wide(int epi, long N) {
+  return epi >= 2 && N % 8 == 0;
+}
+
+// gemm_bt_kernel launch over the (DB, WIDE) variants of one bf16 path
+template <bool STRIDED>
+static void launch_bt(bool db, bool wide, int grid, hipStream_t stream,
+                      const bf16* A, const bf16* B, void* C, long M, long N,
+                      long K, int nbm, int nbn, const StrideMap& sm,
+                      float* stats, int epi) {
+#define AMDTRAIN_BT(DBV, WV)                                                \
+  gemm_bt_kernel<false, STRIDED, false, false, DBV, false, WV>              \
+      <<<grid, GEMM_TPB, 0, stream>>>(A, B, C, M, N, K, nbm, nbn, sm,       \
+                                      stats, epi)
+  if (db && wide) AMDTRAIN_BT(true, true);
+  else if (db) AMDTRAIN_BT(true, false);
+  else if (wide) AMDTRAIN_BT(false, true);
+  else AMDTRAIN_BT(false, false);
+#undef AMDTRAIN_BT
+}
+
+static void launch_bt_n2(bool db, bool wide, int grid, hipStream_t stream,
+                         const bf16* A, const bf16* B, bf16* C, long M,
+                         long N, long K, int nbm, int nbn2, float* stats,
+                         int epi) {
+#define AMDTRAIN_N2(DBV, WV)                                                \
+  gemm_bt_n2_kernel<DBV, WV><<<grid, GEMM_TPB, 0, stream>>>(                \
+      A, B, C, M, N, K, nbm, nbn2, stats, nbm, epi)
+  if (db && wide) AMDTRAIN_N2(true, true);
+  else if (db) AMDTRAIN_N2(true, false);
+  else if (wide) AMDTRAIN_N2(false, true);
+  else AMDTRAIN_N2(false, false);
+#undef AMDTRAIN_N2
+}
+
 at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
                    std::optional<at::Tensor> addend,
-                   std::optional<at::Tensor> bias) {
+                   std::optional<at::Tensor> bias, long epi) {
   TORCH_CHECK(A.is_cuda() && A.dim() == 2 && B.dim() == 2);
   TORCH_CHECK(A.scalar_type() == at::kBFloat16 &&
               B.scalar_type() == at::kBFloat16,
@@ -748,21 +792,17 @@ at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
   }
   const long tiles = (long)nbm * nbn;
   const long ksteps = K / BK;
+  const bf16* Ap = (const bf16*)Ac.const_data_ptr();
+  const bf16* Bp = (const bf16*)Bc.const_data_ptr();
   if (!f32_out && !addend && !bias && N % 256 == 0 && K <= 256 &&
       (long)nbm * (nbn / 2) >= 256) {
     // wide-N small-K: dual-n-tile variant (see kernel comment; measured
     // perf-neutral, halves nominal A traffic and launch width)
     int nbn2 = nbn / 2;
-    if (gemm_db_enabled(K))
-      gemm_bt_n2_kernel<true><<<nbm * nbn2, GEMM_TPB, 0, stream>>>(
-          (const bf16*)Ac.const_data_ptr(),
-          (const bf16*)Bc.const_data_ptr(), (bf16*)C.data_ptr(), M, N, K,
-          nbm, nbn2, nullptr, nbm);
-    else
-      gemm_bt_n2_kernel<<<nbm * nbn2, GEMM_TPB, 0, stream>>>(
-          (const bf16*)Ac.const_data_ptr(),
-          (const bf16*)Bc.const_data_ptr(), (bf16*)C.data_ptr(), M, N, K,
-          nbm, nbn2, nullptr, nbm);
+    const int ep2 = epi_mode(epi, EPI_DEFAULT_N2);
+    launch_bt_n2(gemm_db_enabled(K), epi_wide(ep2, N), nbm * nbn2, stream,
+                 Ap, Bp, (bf16*)C.data_ptr(), M, N, K, nbm, nbn2, nullptr,
+                 ep2);
     CHECK_CUDA_OK();
     return C;
   }
@@ -772,8 +812,7 @@ at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
     auto parts = at::empty({ksplit, M * N},
                            Ac.options().dtype(at::kFloat));
     gemm_bt_ks_kernel<<<(int)(tiles * ksplit), GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        parts.data_ptr<float>(), M, N, K, nbm, nbn, ksplit);
+        Ap, Bp, parts.data_ptr<float>(), M, N, K, nbm, nbn, ksplit);
     CHECK_CUDA_OK();
     gemm_ks_collapse_kernel<<<amd_grid(M * N), AMD_TPB, 0, stream>>>(
         (const float*)parts.const_data_ptr(), (bf16*)C.data_ptr(), ksplit,
@@ -790,36 +829,25 @@ at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
     const char* v = std::getenv("AMDTRAIN_GEMM_LDSE");
     return v && v[0] == '1';
   }();
+  const int grid = nbm * nbn, ep = epi_mode(epi, EPI_DEFAULT_BT);
+  const bool wide = epi_wide(ep, N);
   if (f32_out)
-    gemm_bt_kernel<true, false><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr);
+    gemm_bt_kernel<true, false><<<grid, GEMM_TPB, 0, stream>>>(
+        Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr, ep);
   else if (use_ldse && N % 8 == 0)
     gemm_bt_kernel<false, false, false, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, nullptr);
+        <<<grid, GEMM_TPB, 0, stream>>>(Ap, Bp, C.data_ptr(), M, N, K, nbm,
+                                        nbn, sm, nullptr, ep);
   else if (use_nt)
-    gemm_bt_kernel<false, false, true><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr);
+    gemm_bt_kernel<false, false, true><<<grid, GEMM_TPB, 0, stream>>>(
+        Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr, ep);
   else if (gemm_adir_enabled())
     gemm_bt_kernel<false, false, false, false, true, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, nullptr);
-  else if (use_db)
-    gemm_bt_kernel<false, false, false, false, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, nullptr);
+        <<<grid, GEMM_TPB, 0, stream>>>(Ap, Bp, C.data_ptr(), M, N, K, nbm,
+                                        nbn, sm, nullptr, ep);
   else
-    gemm_bt_kernel<false, false><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr);
+    launch_bt<false>(use_db, wide, grid, stream, Ap, Bp, C.data_ptr(), M, N,
+                     K, nbm, nbn, sm, nullptr, ep);
   CHECK_CUDA_OK();
   // rare big-M path with bias/addend (the FC shapes take the split-K
   // collapse above; keep the hot conv epilogue branch-free)
@@ -829,7 +857,7 @@ at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
 }
 
 // 1x1 conv forward + fused per-block BN statistics partials [nbm][2N]
-std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B) {
+std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B, long epi) {
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kBFloat16 &&
               B.scalar_type() == at::kBFloat16);
   auto Ac = A.contiguous();
@@ -842,34 +870,24 @@ std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B) {
   StrideMap sm{0, 0, 0, 0, 1};
   auto stream = at::cuda::getCurrentCUDAStream();
   const bool use_db = gemm_db_enabled(K);
+  const int ep = epi_mode(epi, EPI_DEFAULT_BT);
+  const bf16* Ap = (const bf16*)Ac.const_data_ptr();
+  const bf16* Bp = (const bf16*)Bc.const_data_ptr();
   if (N % 256 == 0 && K <= 256 && (long)nbm * (nbn / 2) >= 256) {
     int nbn2 = nbn / 2;
-    if (use_db)
-      gemm_bt_n2_kernel<true><<<nbm * nbn2, GEMM_TPB, 0, stream>>>(
-          (const bf16*)Ac.const_data_ptr(),
-          (const bf16*)Bc.const_data_ptr(), (bf16*)C.data_ptr(), M, N, K,
-          nbm, nbn2, stats.data_ptr<float>(), nbm);
-    else
-      gemm_bt_n2_kernel<<<nbm * nbn2, GEMM_TPB, 0, stream>>>(
-          (const bf16*)Ac.const_data_ptr(),
-          (const bf16*)Bc.const_data_ptr(), (bf16*)C.data_ptr(), M, N, K,
-          nbm, nbn2, stats.data_ptr<float>(), nbm);
+    const int ep2 = epi_mode(epi, EPI_DEFAULT_N2);
+    launch_bt_n2(use_db, epi_wide(ep2, N), nbm * nbn2, stream, Ap, Bp,
+                 (bf16*)C.data_ptr(), M, N, K, nbm, nbn2,
+                 stats.data_ptr<float>(), ep2);
   } else if (gemm_adir_enabled()) {
     gemm_bt_kernel<false, false, false, false, true, true>
         <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, stats.data_ptr<float>());
-  } else if (use_db) {
-    gemm_bt_kernel<false, false, false, false, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, stats.data_ptr<float>());
+            Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm,
+            stats.data_ptr<float>(), ep);
   } else {
-    gemm_bt_kernel<false, false><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        C.data_ptr(), M, N, K, nbm, nbn, sm, stats.data_ptr<float>());
+    launch_bt<false>(use_db, epi_wide(ep, N), nbm * nbn, stream, Ap, Bp,
+                     C.data_ptr(), M, N, K, nbm, nbn, sm,
+                     stats.data_ptr<float>(), ep);
   }
   CHECK_CUDA_OK();
   return {C, stats};
@@ -879,7 +897,7 @@ std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B) {
 // * w[n', k] — the even-row gather happens inside the A staging (the
 // separate .contiguous() gather copy this replaces cost ~0.5 ms/step)
 at::Tensor gemm_bt_strided(at::Tensor A, at::Tensor B, long Nn, long H,
-                           long W, long stride) {
+                           long W, long stride, long epi) {
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kBFloat16 &&
               B.scalar_type() == at::kBFloat16);
   auto Ac = A.contiguous();
@@ -892,16 +910,11 @@ at::Tensor gemm_bt_strided(at::Tensor A, at::Tensor B, long Nn, long H,
   int nbm = (int)((M + BM - 1) / BM), nbn = (int)((N + BN - 1) / BN);
   StrideMap sm{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride};
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (gemm_db_enabled(K))
-    gemm_bt_kernel<false, true, false, false, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            (const bf16*)Ac.const_data_ptr(),
-            (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K, nbm,
-            nbn, sm, nullptr);
-  else
-    gemm_bt_kernel<false, true><<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-        (const bf16*)Ac.const_data_ptr(), (const bf16*)Bc.const_data_ptr(),
-        C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr);
+  const int ep = epi_mode(epi, EPI_DEFAULT_BT);
+  launch_bt<true>(gemm_db_enabled(K), epi_wide(ep, N), nbm * nbn, stream,
+                  (const bf16*)Ac.const_data_ptr(),
+                  (const bf16*)Bc.const_data_ptr(), C.data_ptr(), M, N, K,
+                  nbm, nbn, sm, nullptr, ep);
   CHECK_CUDA_OK();
   return C;
 }
