@@ -130,11 +130,11 @@ constexpr int tile_bytes() {
 //   m' = 8*((lane>>3)&3) + 4*(lane>>5) + ((lane>>1)&3),
 //   c  = (lane&1)*8 .. +8
 // (inverse of st_byte: lane*16 = r*512 + q*128 + j*32 + c_half*2).
-template <int MODE, int NCOLS, int MC, int NWAVES = 4>
+template <int MODE, int NCOLS, int MC, int NWAVES = 4, bool CUT = false>
 __device__ __forceinline__ void stage_tn2(
     const bf16* __restrict__ g, int ld, long m0, long M, int col0,
     int total_cols, int cin, const TnGeom& geo, const bf16* __restrict__ zp,
-    bf16* lds) {
+    bf16* lds, int ncut = 0) {
   const int t = threadIdx.x;
   const int wave = t / AMD_WAVE, lane = t % AMD_WAVE;
   constexpr int SUBTILES = (MC / 32) * (NCOLS / 16);
@@ -158,6 +158,8 @@ __device__ __forceinline__ void stage_tn2(
     static_assert((NCOLS / 16) % NWAVES == 0, "wave round spans m-blocks");
     const int mb = (ss * NWAVES) / (NCOLS / 16);
     const int cs = (s % (NCOLS / 16)) * 16;  // subtile column base
+    // subtiles wholly past ncut are never read (tn2_kernel, nlive): no DMA
+    if (CUT && col0 + cs >= ncut) continue;
     const int mloc = mb * 32 + mfrag;
     const long m = m0 + mloc;
     const int col = col0 + cs + c_half;
@@ -183,6 +185,141 @@ __device__ __forceinline__ void stage_tn2(
         16, 0, 0);
   }
 }
+
+// ---- incremental gather addressing (AMDTRAIN_TN2_ADDR, default on) --------
+// stage_tn2 above re-derives every gathered address from m for every 16 B
+// unit of every chunk: two 64-bit div/mod pairs per row, tap and kh
+// divisions, four bounds tests and a 64-bit multiply per unit, all under
+// divergent branches — several times the issue slots of the chunk's 32
+// MFMAs.  But a block's chunks are consecutive, so a thread's rows only
+// ever advance by MC, and its columns never change.  TnWalk keeps
+//   per row slot (MC/32):  the tap-0 input pixel (hb, wb) and its byte
+//     address, stepped by MC rows per chunk with two carries (the
+//     row_advance idea of batchnorm.hip), and from (hb, wb) a validity mask:
+//     bit kh set where row hb+kh is inside the image, bit 16+kw likewise;
+//   per column slot (loop-invariant): the tap's byte offset
+//     ((kh*W + kw)*ld + channel)*2 and the two mask bits it needs.
+// A unit is then one AND + compare, one 64-bit add and a select against the
+// zero page.  The bytes staged are exactly stage_tn2's.
+
+// what MC output rows are in input bytes; filled on the host (tn2_make_step)
+struct TnStep {
+  int step;          // (dn*H*W + dh*stride*W + dw*sw) * ld * 2, no carry
+  int cw, ch;        // extra bytes when wo / ho wraps
+  int dhb, dwb;      // dh*stride, dw*sw
+  int hhi, whi;      // first hb / wb past the last output row / column
+  int hspan, wspan;  // Hout*stride, Wout*sw
+  int nlive;         // dY columns >= nlive are padding (AMDTRAIN_TN2_NSKIP)
+};
+
+// bits t of [0, k) with 0 <= b + t < size  (b >= -15, k <= 15)
+__device__ __forceinline__ unsigned tn2_range_mask(int b, int size, int k) {
+  const int lo = max(-b, 0);
+  const int hi = max(min(size - b, k), lo);
+  return (1u << hi) - (1u << lo);
+}
+
+template <int MODE, int NCOLS, int MC, int NWAVES>
+struct TnWalk {
+  static_assert(MODE == 1 || MODE == 2, "gather modes only");
+  static_assert((NCOLS / 16) % NWAVES == 0, "wave round spans m-blocks");
+  static constexpr int NRS = MC / 32;                // row slots
+  static constexpr int NCS = (NCOLS / 16) / NWAVES;  // column slots
+  static constexpr unsigned NEVER = 0x80000000u;     // bit no row mask has
+
+  unsigned long long base[NRS];  // byte address of the tap-0 pixel's row
+  int hb[NRS], wb[NRS];          // its coordinates, may be off-image
+  long mrow;                     // output row of slot 0 (slot mb: + 32*mb)
+  unsigned toff[NCS], sel[NCS];
+
+  __device__ __forceinline__ void init(const bf16* g, int ld, long m0,
+                                       int col0, int total_cols, int cin,
+                                       const TnGeom& geo) {
+    const int lane = threadIdx.x % AMD_WAVE, wave = threadIdx.x / AMD_WAVE;
+    const int r = lane >> 5, q = (lane >> 3) & 3, j = (lane >> 1) & 3;
+    mrow = m0 + q * 8 + r * 4 + j;
+    const bool narrow = m0 + MC <= 0x7fffffffL;  // block-uniform
+#pragma unroll
+    for (int mb = 0; mb < NRS; ++mb) {
+      long n;
+      int ho, wo;
+      if (narrow) {
+        const unsigned m = (unsigned)(mrow + mb * 32);
+        const unsigned t = m / (unsigned)geo.Wout;
+        wo = (int)(m - t * geo.Wout);
+        const unsigned nn = t / (unsigned)geo.Hout;
+        ho = (int)(t - nn * geo.Hout);
+        n = nn;
+      } else {
+        long t = mrow + mb * 32;
+        wo = (int)(t % geo.Wout); t /= geo.Wout;
+        ho = (int)(t % geo.Hout);
+        n = t / geo.Hout;
+      }
+      hb[mb] = ho * geo.stride - geo.pad;
+      wb[mb] = wo * geo.sw - geo.pw;
+      base[mb] = (unsigned long long)g +
+                 ((n * geo.H + hb[mb]) * geo.W + wb[mb]) * (long)ld * 2;
+    }
+#pragma unroll
+    for (int c = 0; c < NCS; ++c) {
+      const int col = col0 + (c * NWAVES + wave) * 16 + (lane & 1) * 8;
+      const bool in = col + 8 <= total_cols;
+      if (MODE == 1) {
+        toff[c] = col * 2;
+        sel[c] = in ? 1u : NEVER;
+      } else {
+        // a unit never spans taps (cin % 8 == 0)
+        const int tap = col / cin;
+        const int kh = tap / geo.kw, kw = tap - kh * geo.kw;
+        toff[c] = ((kh * geo.W + kw) * ld + (col - tap * cin)) * 2;
+        sel[c] = in ? (1u << (kh & 15)) | (0x10000u << (kw & 15)) : NEVER;
+      }
+    }
+  }
+
+  // stage the current chunk (same bytes, same LDS slots as stage_tn2), then
+  // step to the next
+  __device__ __forceinline__ void stage(long M, const TnGeom& geo,
+                                        const TnStep& st,
+                                        const bf16* __restrict__ zp,
+                                        bf16* lds) {
+    const int lane = threadIdx.x % AMD_WAVE, wave = threadIdx.x / AMD_WAVE;
+    unsigned rmask[NRS];
+#pragma unroll
+    for (int mb = 0; mb < NRS; ++mb) {
+      const unsigned in =
+          MODE == 1 ? 1u
+                    : tn2_range_mask(hb[mb], geo.H, geo.kh) |
+                          tn2_range_mask(wb[mb], geo.W, geo.kw) << 16;
+      rmask[mb] = mrow + mb * 32 < M ? in : 0u;
+    }
+#pragma unroll
+    for (int ss = 0; ss < NRS * NCS; ++ss) {
+      const int mb = ss / NCS, c = ss % NCS;
+      const int s = ss * NWAVES + wave;
+      const unsigned long long a = base[mb] + toff[c];
+      const unsigned long long src =
+          (rmask[mb] & sel[c]) == sel[c] ? a : (unsigned long long)zp;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)src,
+          (__attribute__((address_space(3))) unsigned int*)(
+              (char*)lds + s * 1024 + lane * 16),
+          16, 0, 0);
+    }
+    mrow += MC;
+#pragma unroll
+    for (int mb = 0; mb < NRS; ++mb) {
+      wb[mb] += st.dwb;
+      const bool c1 = wb[mb] >= st.whi;
+      wb[mb] -= c1 ? st.wspan : 0;
+      hb[mb] += st.dhb + (c1 ? geo.stride : 0);
+      const bool c2 = hb[mb] >= st.hhi;
+      hb[mb] -= c2 ? st.hspan : 0;
+      base[mb] += (long)(st.step + (c1 ? st.cw : 0) + (c2 ? st.ch : 0));
+    }
+  }
+};
 
 template <int N>
 __device__ __forceinline__ void vmcnt_wait() {
@@ -233,16 +370,25 @@ __device__ __forceinline__ bf16x8 tr_frag(unsigned addr) {
 // BAND: group-diagonal wgrad (grouped conv, Cin == N, both % 128): each
 // n-tile needs only ONE k-tile per tap (its own 128-channel window), so
 // tiles = nbn*9 and the output is the COMPACT [N, 9*NCX] band.
-template <int GMODE, int NW, int KW, int MC, int NBUF = 2, bool BAND = false>
-__global__ void __launch_bounds__(NW * KW * 64, (NW * KW == 4 ? 2 : 1))
+// WALK (gather modes only): X addresses from TnWalk instead of stage_tn2.
+template <int GMODE, int NW, int KW, int MC, int NBUF = 2, bool BAND = false,
+          bool WALK = false>
+__global__ void __launch_bounds__(
+    NW * KW * 64,
+    // the walk's state must not cost (1,4,32) its fourth block per CU
+    // (40 KB LDS): hold it to the 128 VGPRs stage_tn2's version has
+    (WALK && MC == 32 && NBUF == 2 ? 4 : NW * KW == 4 ? 2 : 1))
 tn2_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
            float* __restrict__ parts, long M, int N, int K9, int Cin,
            TnGeom geo, int nbn, int nbk, int msplit,
-           const bf16* __restrict__ zp) {
+           const bf16* __restrict__ zp, TnStep step) {
+  static_assert(!WALK || GMODE != 0, "plain rows have nothing to walk");
   constexpr int NWAVES = NW * KW;  // 4 (256 thr, 2 blk/CU) or 8 (512, 1)
   constexpr int NCY = NW * 64;   // dY tile cols
   constexpr int NCX = KW * 64;   // X tile cols
   constexpr int KSTEPS = MC / 32;
+  // counted vmcnt (NBUF 3) needs every wave to issue every load
+  constexpr bool NSKIP = WALK && NBUF == 2 && NW == 2 && KW == 2;
   // per-thread global_load_lds issues per chunk (both operands):
   // subtiles = (MC/32)*(cols/16) per operand, one wave-round each
   constexpr int LC = (MC / 32) * (NCY / 16 + NCX / 16) * 64 / (NW * KW * 64);
@@ -286,15 +432,33 @@ tn2_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
     constexpr unsigned YB = tile_bytes<NCY, MC>();
     constexpr unsigned XB = tile_bytes<NCX, MC>();
 
-    stage_tn2<0, NCY, MC, NWAVES>(dY, N, mc0 * MC, M, n0, N, Cin, geo, zp,
-                                  (bf16*)Ys[0]);
-    stage_tn2<GMODE, NCX, MC, NWAVES>(X, Cin, mc0 * MC, M, k0, K9, Cin, geo,
-                                      zp, (bf16*)Xs[0]);
+    // X chunks are staged in order mc0, mc0 + 1, ...: the walk starts at
+    // mc0 and every stage_x call moves it one chunk on
+    TnWalk<WALK ? GMODE : 1, NCX, MC, NWAVES> xw;
+    if constexpr (WALK) xw.init(X, Cin, mc0 * MC, k0, K9, Cin, geo);
+    auto stage_x = [&](long mch, char* dst) {
+      if constexpr (WALK)
+        xw.stage(M, geo, step, zp, (bf16*)dst);
+      else
+        stage_tn2<GMODE, NCX, MC, NWAVES>(X, Cin, mch * MC, M, k0, K9, Cin,
+                                          geo, zp, (bf16*)dst);
+    };
+
+    // NSKIP: where N <= 64 leaves the upper half of the 128-wide dY tile
+    // padding, its subtiles are not staged and the waves that own it (their
+    // results are never stored) skip their tr-reads and MFMAs
+    auto stage_y = [&](long mch, char* dst) {
+      stage_tn2<0, NCY, MC, NWAVES, NSKIP>(dY, N, mch * MC, M, n0, N, Cin, geo,
+                                           zp, (bf16*)dst, step.nlive);
+    };
+    const bool live =
+        !NSKIP || __builtin_amdgcn_readfirstlane(n0 + wn) < step.nlive;
+
+    stage_y(mc0, Ys[0]);
+    stage_x(mc0, Xs[0]);
     if (NBUF >= 3 && mc0 + 1 < mc1) {
-      stage_tn2<0, NCY, MC, NWAVES>(dY, N, (mc0 + 1) * MC, M, n0, N, Cin,
-                                    geo, zp, (bf16*)Ys[1]);
-      stage_tn2<GMODE, NCX, MC, NWAVES>(X, Cin, (mc0 + 1) * MC, M, k0, K9,
-                                        Cin, geo, zp, (bf16*)Xs[1]);
+      stage_y(mc0 + 1, Ys[1]);
+      stage_x(mc0 + 1, Xs[1]);
       vmcnt_wait<LC>();  // chunk 0 complete; chunk 1 may stay in flight
     } else {
       vmcnt_wait<0>();
@@ -306,15 +470,14 @@ tn2_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
       const long pre = NBUF >= 3 ? mc + 2 : mc + 1;
       if (pre < mc1) {
         const int nxt = (int)((pre - mc0) % NBUF);
-        stage_tn2<0, NCY, MC, NWAVES>(dY, N, pre * MC, M, n0, N, Cin, geo,
-                                      zp, (bf16*)Ys[nxt]);
-        stage_tn2<GMODE, NCX, MC, NWAVES>(X, Cin, pre * MC, M, k0, K9, Cin,
-                                          geo, zp, (bf16*)Xs[nxt]);
+        stage_y(pre, Ys[nxt]);
+        stage_x(pre, Xs[nxt]);
       }
       const unsigned yb = ybase0 + cur * YB;
       const unsigned xb = xbase0 + cur * XB;
 #pragma unroll
       for (int ks = 0; ks < KSTEPS; ++ks) {
+        if (!live) break;  // wave-uniform
         bf16x8 a[4], b[4];
         // each 16-col subtile is 2 groups; the m-half (ks) advances by a
         // full row of subtiles
@@ -413,6 +576,47 @@ static at::Tensor tn2_zero_page(const at::Tensor& like) {
   return zp;
 }
 
+// AMDTRAIN_TN2_ADDR=0: the gather modes derive every address from m again
+// (stage_tn2) — the reference of the equality tests and the A/B.  Read per
+// call, like AMDTRAIN_TN2_BLOCKS.
+static bool tn2_walk_enabled() {
+  const char* v = std::getenv("AMDTRAIN_TN2_ADDR");
+  return !(v && v[0] == '0');
+}
+
+// AMDTRAIN_TN2_NSKIP=0: stage and multiply the padded half of the dY tile
+// where N <= 64, as before (A/B; the outputs are the same either way)
+static bool tn2_nskip_enabled() {
+  const char* v = std::getenv("AMDTRAIN_TN2_NSKIP");
+  return !(v && v[0] == '0');
+}
+
+// The steps of TnWalk for chunks of MC rows over rows of ld elements.
+// Returns false where the walk's 32-bit offsets or 15-bit masks do not hold
+// the geometry (no conv here comes near); stage_tn2 then serves it.
+static bool tn2_make_step(const TnGeom& g, int MC, int ld, int N,
+                          TnStep* st) {
+  const long hw = (long)g.Hout * g.Wout;
+  const long dn = MC / hw, rem = MC % hw;
+  const long dh = rem / g.Wout, dw = rem % g.Wout;
+  const long step =
+      (dn * g.H * g.W + dh * g.stride * g.W + dw * g.sw) * ld * 2;
+  const long cw = ((long)g.stride * g.W - (long)g.Wout * g.sw) * ld * 2;
+  const long ch = ((long)g.H * g.W - (long)g.Hout * g.stride * g.W) * ld * 2;
+  const long tap = ((long)g.kh * g.W + g.kw + 1) * ld * 2;
+  const long lim = 1L << 29;  // step + cw + ch and base + tap stay in range
+  if (std::abs(step) >= lim || std::abs(cw) >= lim || std::abs(ch) >= lim ||
+      tap >= lim || g.kh > 15 || g.kw > 15 || g.pad > 15 || g.pw > 15 ||
+      g.pad < 0 || g.pw < 0)
+    return false;
+  *st = TnStep{(int)step, (int)cw, (int)ch,
+               (int)(dh * g.stride), (int)(dw * g.sw),
+               g.Hout * g.stride - g.pad, g.Wout * g.sw - g.pw,
+               g.Hout * g.stride, g.Wout * g.sw,
+               tn2_nskip_enabled() ? N : 0x7fffffff};
+  return true;
+}
+
 template <int GMODE, int NW, int KW, int MC, int NBUF = 2>
 void tn2_launch(const at::Tensor& dY, const at::Tensor& X, at::Tensor& out,
                 long M, int N, int K9, int Cin, TnGeom geo, int target_blocks,
@@ -427,11 +631,24 @@ void tn2_launch(const at::Tensor& dY, const at::Tensor& X, at::Tensor& out,
   at::Tensor parts = out;
   if (msplit > 1)
     parts = at::empty({msplit, (long)N * K9}, out.options());
-  tn2_kernel<GMODE, NW, KW, MC, NBUF>
-      <<<(int)(tiles * msplit), NW * KW * 64, 0, stream>>>(
-          (const bf16*)dY.const_data_ptr(), (const bf16*)X.const_data_ptr(),
-          parts.data_ptr<float>(), M, N, K9, Cin, geo, nbn, nbk, msplit,
-          (const bf16*)zp.const_data_ptr());
+  TnStep st{};
+  bool walk = false;
+  if constexpr (GMODE != 0)
+    walk = tn2_walk_enabled() && tn2_make_step(geo, MC, Cin, N, &st);
+  auto launch = [&](auto kernel) {
+    kernel<<<(int)(tiles * msplit), NW * KW * 64, 0, stream>>>(
+        (const bf16*)dY.const_data_ptr(), (const bf16*)X.const_data_ptr(),
+        parts.data_ptr<float>(), M, N, K9, Cin, geo, nbn, nbk, msplit,
+        (const bf16*)zp.const_data_ptr(), st);
+  };
+  if constexpr (GMODE != 0) {
+    if (walk)
+      launch(tn2_kernel<GMODE, NW, KW, MC, NBUF, false, true>);
+    else
+      launch(tn2_kernel<GMODE, NW, KW, MC, NBUF>);
+  } else {
+    launch(tn2_kernel<GMODE, NW, KW, MC, NBUF>);
+  }
   CHECK_CUDA_OK();
   if (msplit > 1) {
     const long NK = (long)N * K9;
@@ -515,6 +732,9 @@ at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
     // fits the 256-wide k-tile of (1,4,32) whole, so dY is staged once:
     // 0.63 ms against 0.82 ms on (2,2,64) and 1.45 ms for the 49-tap form
     // (b512, tools/bench_wgrad.py --stem; AMDTRAIN_TN2_STEM22 forces (2,2,64))
+    // Those figures predate TnWalk.  On the walk (bench_wgrad.py --configs):
+    // layer-1 3x3 254 us here against 253 us on (1,4,32), a tie; the stems
+    // 625 / 352 us on (1,4,32) against 760 / 396 us on (2,2,64).
     if (gmode == 2 && Cin >= 32 && std::getenv("AMDTRAIN_TN2_14") == nullptr)
       tn2_launch<2, 2, 2, 64>(Yc, Xc, out, M, N, K9, Cin, geo, target, stream);
     else if (gmode == 2 && std::getenv("AMDTRAIN_TN2_STEM22") != nullptr)
@@ -532,14 +752,15 @@ at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
       const char* v = std::getenv("AMDTRAIN_TN2_PIPE3");
       return v && v[0] == '1';
     }();
-    static const bool wide8 = []() {  // A/B override
+    static const int w8 = []() {  // A/B override: 1 always, 0 never
       const char* v = std::getenv("AMDTRAIN_TN2_W8");
-      return v && v[0] == '1';
+      return v && v[0] == '1' ? 1 : v && v[0] == '0' ? 0 : -1;
     }();
+    const bool wide8 = w8 == 1;
     // 8-wave (2m x 4k) block halves dY re-reads (two k-tiles per staged
     // chunk); measured +11% at deep-K (K9=4608 layer4 3x3), flat at
     // smaller K (L3 already absorbs those re-reads) -> auto for K>=4096
-    if ((wide8 || (gmode == 2 && K9 >= 4096)) && K9 % 256 == 0
+    if ((wide8 || (w8 != 0 && gmode == 2 && K9 >= 4096)) && K9 % 256 == 0
         && gmode != 1) {
       if (gmode == 2)
         tn2_launch<2, 2, 4, 64>(Yc, Xc, out, M, N, K9, Cin, geo, target,
@@ -602,11 +823,18 @@ at::Tensor tn2_wgrad_banded(at::Tensor dY, at::Tensor X, long Nn, long H,
   at::Tensor parts = out;
   if (msplit > 1)
     parts = at::empty({msplit, (long)N * 9 * 128}, out.options());
-  tn2_kernel<2, 2, 2, 64, 2, true>
-      <<<(int)(tiles * msplit), TN2_TPB, 0, stream>>>(
-          (const bf16*)Yc.const_data_ptr(), (const bf16*)Xc.const_data_ptr(),
-          parts.data_ptr<float>(), M, N, 9 * Cin, Cin, geo, nbn, nbk, msplit,
-          (const bf16*)zp.const_data_ptr());
+  TnStep st{};
+  const bool walk = tn2_walk_enabled() && tn2_make_step(geo, 64, Cin, N, &st);
+  auto launch = [&](auto kernel) {
+    kernel<<<(int)(tiles * msplit), TN2_TPB, 0, stream>>>(
+        (const bf16*)Yc.const_data_ptr(), (const bf16*)Xc.const_data_ptr(),
+        parts.data_ptr<float>(), M, N, 9 * Cin, Cin, geo, nbn, nbk, msplit,
+        (const bf16*)zp.const_data_ptr(), st);
+  };
+  if (walk)
+    launch(tn2_kernel<2, 2, 2, 64, 2, true, true>);
+  else
+    launch(tn2_kernel<2, 2, 2, 64, 2, true>);
   CHECK_CUDA_OK();
   if (msplit > 1) {
     const long NK = (long)N * 9 * 128;

@@ -5,7 +5,13 @@ b512 wgrad shapes, refchecked vs fp32 matmul.
 ``--stem`` instead times the 7x7 stem at batch BENCH_B: the 49-tap
 channel-padded forward and wgrad against the width space-to-depth form,
 whose wgrad runs on the (1,4,32) and, with AMDTRAIN_TN2_STEM22, the
-(2,2,64) wave grid."""
+(2,2,64) wave grid.
+
+``--addr`` times every gathered-X wgrad of the step (3x3, strided 1x1,
+both stem forms) with the direct address code (AMDTRAIN_TN2_ADDR=0) and
+the incremental walk, alternated in one process; ``--configs`` times the
+tile choices (AMDTRAIN_TN2_14, _STEM22; run it again under
+AMDTRAIN_TN2_W8=0/1 and AMDTRAIN_TN2_PIPE3=1, which are read once)."""
 import os
 import sys
 import time
@@ -138,8 +144,115 @@ def run_stem():
           f"({flops/t/1e12:6.1f} useful TF)")
 
 
+def ab_env(fn, variants, rounds=3, iters=30):
+    """fn timed under each {env} of variants, alternated over rounds in
+    this process (the tn2 switches named here are read per call); fastest
+    round per variant, plus whether every variant returns the same bits"""
+    best = {k: float("inf") for k in variants}
+    outs = {}
+    for _ in range(rounds):
+        for k, env in variants.items():
+            os.environ.update(env)
+            outs[k] = fn()
+            best[k] = min(best[k], time_fn(fn, iters))
+            for name in env:
+                del os.environ[name]
+    ref = next(iter(outs.values()))
+    same = all(torch.equal(ref, o) for o in outs.values())
+    return best, same
+
+
+def gather_sites():
+    """(label, calls per step, flops, call) of every gathered-X wgrad of a
+    ResNet-50 step at batch B: the 3x3 convs, both stem forms and the
+    strided 1x1 downsample convs"""
+    from amdtrain.ops.conv import stem_s2d_input
+    sites = []
+    for cnt, (cin, cout, hw, s) in [
+            (3, (64, 64, 56, 1)),
+            (1, (128, 128, 56, 2)), (3, (128, 128, 28, 1)),
+            (1, (256, 256, 28, 2)), (5, (256, 256, 14, 1)),
+            (1, (512, 512, 14, 2)), (2, (512, 512, 7, 1))]:
+        ho = (hw + 2 - 3) // s + 1
+        M = B * ho * ho
+        x2d = torch.randn(B * hw * hw, cin, device="cuda").bfloat16()
+        gy2d = torch.randn(M, cout, device="cuda").bfloat16()
+        sites.append((
+            f"3x3 {cin}->{cout} {hw}x{hw}/{s}", cnt, 2.0 * M * cout * 9 * cin,
+            lambda gy2d=gy2d, x2d=x2d, hw=hw, s=s:
+                _C.tn2_wgrad(gy2d, x2d, 9, B, hw, hw, s, 2)))
+    for cin, cout, hw in [(256, 512, 56), (512, 1024, 28), (1024, 2048, 14)]:
+        M = B * (hw // 2) ** 2
+        x2d = torch.randn(B * hw * hw, cin, device="cuda").bfloat16()
+        gy2d = torch.randn(M, cout, device="cuda").bfloat16()
+        sites.append((
+            f"1x1/2 {cin}->{cout} {hw}x{hw}", 1, 2.0 * M * cout * cin,
+            lambda gy2d=gy2d, x2d=x2d, hw=hw:
+                _C.tn2_wgrad(gy2d, x2d, 1, B, hw, hw, 2, 1)))
+    H = 224
+    Ho = H // 2
+    gy = torch.randn(B * Ho * Ho, 64, device="cuda").bfloat16()
+    x = torch.randn(B, H, H, 3, device="cuda").bfloat16()
+    x8 = torch.nn.functional.pad(x, (0, 5)).view(B * H * H, 8)
+    xs = stem_s2d_input(x).view(B * H * (H // 2), 8)
+    flops = 2.0 * B * Ho * Ho * 64 * 147
+    sites.append(("stem 49-tap", 1, flops,
+                  lambda: _C.tn2_wgrad(gy, x8, 49, B, H, H, 2, 2, 7, 7, 3)))
+    sites.append(("stem s2d 28-tap (not default)", 0, flops,
+                  lambda: _C.tn2_wgrad(gy, xs, 28, B, H, H // 2, 2, 2, 7, 4,
+                                       3, 1, 2, Ho, Ho)))
+    return sites
+
+
+def run_addr():
+    """AMDTRAIN_TN2_ADDR=0 (every address derived from m) against the
+    incremental walk, and the walk with AMDTRAIN_TN2_NSKIP=0"""
+    torch.manual_seed(0)
+    variants = {"direct": {"AMDTRAIN_TN2_ADDR": "0"},
+                "walk": {"AMDTRAIN_TN2_ADDR": "1"},
+                "walk, no N skip": {"AMDTRAIN_TN2_NSKIP": "0"}}
+    print(f"== gathered-X wgrads at batch {B}: us (useful TF) ==")
+    print("| site (calls/step) | " + " | ".join(variants) + " | same bits |")
+    print("|---|" + "---|" * (len(variants) + 1))
+    tot = {k: 0.0 for k in variants}
+    for label, cnt, flops, fn in gather_sites():
+        best, same = ab_env(fn, variants)
+        for k in variants:
+            tot[k] += cnt * best[k]
+        cells = [f"{best[k]*1e6:.1f} ({flops/best[k]/1e12:.0f})"
+                 for k in variants]
+        print(f"| {label} ({cnt}) | " + " | ".join(cells) +
+              f" | {'yes' if same else 'NO'} |", flush=True)
+    print("| weighted per step | " +
+          " | ".join(f"{tot[k]*1e6:.0f}" for k in variants) + " | |")
+
+
+def run_configs():
+    """The tile decisions taken while the m-loop was address-bound, timed
+    again on the walk.  AMDTRAIN_TN2_W8 and AMDTRAIN_TN2_PIPE3 are read
+    once per process: set them outside and compare the 'default' column
+    across runs."""
+    torch.manual_seed(0)
+    variants = {"default": {}, "TN2_14": {"AMDTRAIN_TN2_14": "1"},
+                "STEM22": {"AMDTRAIN_TN2_STEM22": "1"}}
+    held = {k: os.environ[k] for k in ("AMDTRAIN_TN2_W8", "AMDTRAIN_TN2_PIPE3")
+            if k in os.environ}
+    print(f"== tn2 configurations at batch {B}, process-wide {held}: us ==")
+    print("| site | " + " | ".join(variants) + " |")
+    print("|---|" + "---|" * len(variants))
+    for label, cnt, flops, fn in gather_sites():
+        best, _ = ab_env(fn, variants)
+        print(f"| {label} | " +
+              " | ".join(f"{best[k]*1e6:.1f}" for k in variants) + " |",
+              flush=True)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--stem":
         run_stem()
+    elif len(sys.argv) > 1 and sys.argv[1] == "--addr":
+        run_addr()
+    elif len(sys.argv) > 1 and sys.argv[1] == "--configs":
+        run_configs()
     else:
         main()
