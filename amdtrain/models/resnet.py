@@ -21,7 +21,7 @@ MI355X-first details:
 
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Type, Union
+from typing import List, Optional, Type, Union
 
 import torch
 import torch.nn as nn
@@ -249,27 +249,3 @@ def resnext50_32x4d(num_classes: int = 1000, **kw) -> ResNet:
 def wide_resnet50_2(num_classes: int = 1000, **kw) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes=num_classes,
                   width_per_group=128, **kw)
-
-
-_REGISTRY: Dict[str, Callable[..., nn.Module]] = {
-    "resnet18": resnet18,
-    "resnet34": resnet34,
-    "resnet50": resnet50,
-    "resnet101": resnet101,
-    "resnet152": resnet152,
-    "resnext50_32x4d": resnext50_32x4d,
-    "wide_resnet50_2": wide_resnet50_2,
-}
-
-
-def model_names() -> List[str]:
-    """Sorted architecture names, for the ``-a/--arch`` choices list
-    (reference distributed.py:21-23)."""
-    return sorted(_REGISTRY)
-
-
-def build_model(arch: str, num_classes: int = 1000, **kw) -> nn.Module:
-    """``torchvision.models.__dict__[arch]()`` equivalent (distributed.py:134-139)."""
-    if arch not in _REGISTRY:
-        raise ValueError(f"unknown arch '{arch}'; choices: {model_names()}")
-    return _REGISTRY[arch](num_classes=num_classes, **kw)

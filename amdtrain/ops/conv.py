@@ -401,6 +401,60 @@ def conv3x3_grouped_mfma(x: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+class _DwConv3x3(torch.autograd.Function):
+    """Depthwise 3x3 pad-1 conv (stride 1/2) over the vectorised stencil
+    kernels of dwconv.hip: forward, gather-form input gradient and a
+    two-level fixed-order weight gradient, all NHWC bf16 with fp32
+    accumulation.  The kernels take the weight tap-major, ``w9`` [9, C]."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+        e = require_ext()
+        n, c, h, w = x.shape
+        xc = x.to(torch.bfloat16) \
+            .contiguous(memory_format=torch.channels_last)
+        x2d = _rows(xc)
+        wb = weight.to(torch.bfloat16)
+        w9 = wb.reshape(c, 9).t().contiguous()
+        y2d = e.dwconv3x3_fwd(x2d, n, h, w, stride, w9)
+        ctx.save_for_backward(x2d, wb)
+        ctx.meta = (n, c, h, w, stride)
+        ho = (h + 2 - 3) // stride + 1
+        wo = (w + 2 - 3) // stride + 1
+        return y2d.view(n, ho, wo, c).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor):
+        e = require_ext()
+        x2d, wb = ctx.saved_tensors
+        n, c, h, w, stride = ctx.meta
+        gy = grad_y.contiguous(memory_format=torch.channels_last)
+        gy2d = _rows(gy).to(torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            w9 = wb.reshape(c, 9).t().contiguous()
+            dx2d = e.dwconv3x3_dgrad(gy2d, n, h, w, stride, w9)
+            dx = dx2d.view(n, h, w, c).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw9 = e.dwconv3x3_wgrad(gy2d, x2d, n, h, w, stride)  # [9, C] f32
+            dw = dw9.t().reshape(c, 1, 3, 3)
+        return dx, dw, None
+
+
+def dwconv3x3(x: torch.Tensor, weight: torch.Tensor,
+              stride: int = 1) -> torch.Tensor:
+    """Depthwise 3x3 pad-1 conv, ``weight`` [C, 1, 3, 3], stride 1 or 2.
+    On the GPU with the extension loaded: the bf16 stencil kernels (C must
+    be a multiple of 8).  On CPU, or with the extension off: exactly
+    ``F.conv2d(..., groups=C)``."""
+    if x.is_cuda and ext_available():
+        return _DwConv3x3.apply(x, weight, stride)
+    return torch.nn.functional.conv2d(x, weight, None, stride, 1, 1,
+                                      x.shape[1])
+
+
 def stem_s2d_input(x_nhwc: torch.Tensor) -> torch.Tensor:
     """[N, H, W, C] (C <= 4, W even) -> X' [N, H, W/2, 8]: channels padded
     to 4, then two neighbouring pixels share one 8-channel row, channel
@@ -569,9 +623,14 @@ class AmdConv2d(nn.Conv2d):
     1x1 -> MFMA GEMM (gemm.hip), 3x3 pad-1 s1/s2 -> implicit GEMM
     (conv3x3.hip), anything else without an input gradient (the 7x7
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
-    Grouped/dilated convs and fp32 inference fall through to MIOpen.
-    Env overrides AMDTRAIN_CONV1X1 / AMDTRAIN_CONV3X3 / AMDTRAIN_CONVSTEM
-    = "miopen" for A/B measurement.
+    Depthwise 3x3 pad-1 s1/s2 (groups == in == out channels, C % 8 == 0)
+    -> vectorised stencil (dwconv.hip); other grouped 3x3 with
+    in % 32 == 0 and out % 16 == 0 (ResNeXt) -> block-diagonalized dense
+    conv3x3.  Every other grouped conv, dilated convs, convs with a bias
+    and fp32 inference fall through to MIOpen.
+    Env overrides AMDTRAIN_CONV1X1 / AMDTRAIN_CONV3X3 / AMDTRAIN_CONV3X3G /
+    AMDTRAIN_CONVSTEM / AMDTRAIN_DWCONV = "miopen" for A/B measurement,
+    read on every call.
     """
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -582,6 +641,15 @@ class AmdConv2d(nn.Conv2d):
         if (x.is_cuda and bf16_ok and ext_available()
                 and self.bias is None and self.dilation == (1, 1)
                 and self.groups > 1):
+            # depthwise 3x3: vectorised stencil, not a GEMM
+            if (self.groups == self.in_channels == self.out_channels
+                    and self.kernel_size == (3, 3)
+                    and self.padding == (1, 1)
+                    and self.stride in ((1, 1), (2, 2))
+                    and self.in_channels % 8 == 0):
+                if os.environ.get("AMDTRAIN_DWCONV", "custom") == "miopen":
+                    return super().forward(x)
+                return dwconv3x3(x, self.weight, self.stride[0])
             # grouped 3x3 (ResNeXt): block-diagonalized dense path
             if (self.kernel_size == (3, 3) and self.padding == (1, 1)
                     and self.stride[0] in (1, 2)

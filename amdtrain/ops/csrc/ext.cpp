@@ -136,6 +136,14 @@ at::Tensor max_pool_3x3_s2_bwd(at::Tensor grad_y, at::Tensor idx, long H,
 at::Tensor global_avg_pool_fwd(at::Tensor x);
 at::Tensor global_avg_pool_bwd(at::Tensor grad_y, long H, long W);
 
+// dwconv.hip
+at::Tensor dwconv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
+                         at::Tensor w9);
+at::Tensor dwconv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
+                           long stride, at::Tensor w9);
+at::Tensor dwconv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
+                           long W, long stride);
+
 // epi (trailing, defaulted): AMDTRAIN_EPILOGUE mode of the bf16 C store,
 // 0 / 1 / 2 (csrc/common.h); -1 = each kernel's measured default
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -229,4 +237,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("max_pool_3x3_s2_bwd", &max_pool_3x3_s2_bwd);
   m.def("global_avg_pool_fwd", &global_avg_pool_fwd);
   m.def("global_avg_pool_bwd", &global_avg_pool_bwd);
+  m.def("dwconv3x3_fwd", &dwconv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w9"));
+  m.def("dwconv3x3_dgrad", &dwconv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w9"));
+  m.def("dwconv3x3_wgrad", &dwconv3x3_wgrad, py::arg("dy2d"),
+        py::arg("x2d"), py::arg("Nn"), py::arg("H"), py::arg("W"),
+        py::arg("stride"));
 }

@@ -30,6 +30,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "gemm8p.hip"),
         os.path.join(CSRC, "wgrad.hip"),
         os.path.join(CSRC, "pool.hip"),
+        os.path.join(CSRC, "dwconv.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
