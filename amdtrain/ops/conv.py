@@ -1,10 +1,14 @@
-"""Hand-written 1x1 convolution over the gfx950 MFMA GEMM kernels.
+"""Hand-written convolutions over the gfx950 MFMA GEMM kernels.
 
 A 1x1 conv on NHWC data is exactly a GEMM over rows R = N*H*W
 (SURVEY §2c): forward C[R,Cout] = X[R,Cin] x W[Cout,Cin]^T, dgrad uses the
-pre-transposed weight, wgrad is the TN GEMM with split-M accumulation.
-Strided (downsample) 1x1 convs gather/scatter the even rows around the same
-GEMMs.
+pre-transposed weight.  Strided (downsample) 1x1 convs gather/scatter the
+even rows around the same GEMMs.  3x3, grouped 3x3 and the generic (stem)
+convs are implicit GEMMs over the same tiles.
+
+Every weight gradient is tn2_wgrad (wgrad.hip): one launch, split-M fp32
+partials collapsed in a fixed order, so it has no atomics and is bitwise
+deterministic.
 
 Dispatch: ``AmdConv2d`` routes all eligible convs (GPU + extension + bf16
 path) to the hand-written kernels; see the class docstring for the matrix.
@@ -75,13 +79,6 @@ def _epilogue_mode() -> int:
     if mode not in (0, 1, 2):
         raise ValueError(f"AMDTRAIN_EPILOGUE must be 0, 1 or 2, got {v!r}")
     return mode
-
-
-def _wgrad2_enabled() -> bool:
-    """tn2_wgrad (wgrad.hip): tr-read TN core — single launch for all 9
-    conv3x3 taps, no atomics, bitwise deterministic.  Default on;
-    AMDTRAIN_WGRAD2=0 falls back to the round-1 per-tap kernels for A/B."""
-    return os.environ.get("AMDTRAIN_WGRAD2", "1") == "1"
 
 
 class GradCell:
@@ -222,13 +219,10 @@ class _Conv1x1(torch.autograd.Function):
                 # fused zero+scatter (one write pass; stride-2 only in
                 # ResNet)
                 dx = e.scatter_rows_x2(dx2d, n, h, w, ho, wo)
-            dw = e.tn2_wgrad(gy2d, x2d, 1, n, h, w, stride, 1) \
-                if _wgrad2_enabled() \
-                else e.gemm_tn_strided(gy2d, x2d, n, h, w, stride)
+            dw = e.tn2_wgrad(gy2d, x2d, 1, n, h, w, stride, 1)
         else:
             dx = dx2d.view(n, ho, wo, cin).permute(0, 3, 1, 2)
-            dw = e.tn2_wgrad(gy2d, x2d) if _wgrad2_enabled() \
-                else e.gemm_tn(gy2d, x2d, 0)
+            dw = e.tn2_wgrad(gy2d, x2d)
         return dx, dw.reshape(cout, cin, 1, 1), None, None
 
 
@@ -287,9 +281,7 @@ class _Conv3x3(torch.autograd.Function):
                                _epilogue_mode())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         # [Cout, 9*Cin] f32 — single-launch tap-gather TN (wgrad.hip)
-        dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2) \
-            if _wgrad2_enabled() \
-            else e.conv3x3_wgrad(gy2d, x2d, n, h, w, stride)
+        dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2)
         # back to [Cout,Cin,3,3] (channels_last layout of the weight)
         dw = dw2d.view(cout, 3, 3, cin).permute(0, 3, 1, 2) \
             .contiguous(memory_format=torch.channels_last)
@@ -370,7 +362,7 @@ class _ConvGrouped3x3(torch.autograd.Function):
                                _s2parity_enabled(), _nt64_enabled(),
                                _epilogue_mode())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        if banded and _wgrad2_enabled():
+        if banded:
             # compact band [Cout, 9, 128]: extract the group diagonal of
             # each 128-channel window
             dwb = e.tn2_wgrad_banded(gy2d, x2d, n, h, w, stride) \
@@ -381,9 +373,7 @@ class _ConvGrouped3x3(torch.autograd.Function):
                 .view(cout, 3, 3, sg).permute(0, 3, 1, 2) \
                 .contiguous(memory_format=torch.channels_last)
             return dx, dw, None, None
-        dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2) \
-            if _wgrad2_enabled() \
-            else e.conv3x3_wgrad(gy2d, x2d, n, h, w, stride)
+        dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2)
         # slice the group diagonal of the dense dW
         dwd = dw2d.view(groups, sout, 3, 3, groups, sg)
         gi = torch.arange(groups, device=dwd.device)
@@ -584,26 +574,23 @@ class _ConvGeneric(torch.autograd.Function):
                               1, 2, ho, wo)              # [Cout, 224] f32
             dw = stem_s2d_dweight(dwp, cin) \
                 .contiguous(memory_format=torch.channels_last)
-        elif _wgrad2_enabled() and cout % 8 == 0:
+        else:
             # tap-gather TN core; x2d is already channel-padded (fwd)
             dwp = e.tn2_wgrad(gy2d, x2d, kh * kw, n, h, w, stride, 2,
                               kh, kw, pad)               # [Cout, taps*cin_k]
             dw = dwp.view(cout, kh * kw, cin_k)[:, :, :cin] \
                 .view(cout, kh, kw, cin).permute(0, 3, 1, 2) \
                 .contiguous(memory_format=torch.channels_last)
-        else:
-            dw2 = e.conv_generic_wgrad(gy2d, x2d, n, h, w, kh, kw, stride,
-                                       pad)
-            dw = dw2[:, :k].view(cout, kh * kw, cin_k)[:, :, :cin] \
-                .reshape(cout, kh, kw, cin).permute(0, 3, 1, 2) \
-                .contiguous(memory_format=torch.channels_last)
         return dx, dw, None, None, None, None
 
 
 def conv_stem_mfma(x: torch.Tensor, weight: torch.Tensor, stride: int,
                    pad: int) -> torch.Tensor:
-    # the s2d weight gradient exists in the tap-gather TN core only
-    s2d = (_stem_s2d_enabled() and _wgrad2_enabled()
+    """Generic-path conv (the 7x7 stem and odd configurations).  The weight
+    gradient is the tap-gather tn2_wgrad, which needs ``cout % 8 == 0``
+    (``AmdConv2d`` only routes ``out_channels % 16 == 0`` here); a direct
+    caller with another ``cout`` gets tn2_wgrad's error in backward."""
+    s2d = (_stem_s2d_enabled()
            and _stem_s2d_ok(weight, x.shape[3], stride, pad))
     y, stats = _ConvGeneric.apply(x, weight, stride, pad, s2d,
                                   _stem_nt64_enabled())

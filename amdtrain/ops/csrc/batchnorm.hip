@@ -13,7 +13,8 @@
 // Reduction strategy (CDNA4): rows R = N*H*W of C contiguous channels;
 // 16 B/lane vector loads; each thread owns a FIXED channel-group so partial
 // sums live in registers (no LDS atomics in the hot loop), then one LDS
-// phase-reduction per block and one global atomicAdd per channel per block.
+// phase-reduction per block into per-block partials that a second stage
+// sums in a fixed order (no global atomics).
 // All ResNet channel counts (64..2048) hit this register path.
 #include <cstdlib>
 #include <cstring>

@@ -1,12 +1,11 @@
 // Implicit-GEMM 3x3 convolution (NHWC, pad 1, stride 1/2) for gfx950 —
-// forward, dgrad and wgrad (SURVEY §2c "Conv2d 3x3 ... 16 call sites/fwd").
+// forward and dgrad (SURVEY §2c "Conv2d 3x3 ... 16 call sites/fwd"); the
+// weight gradient is the 9-tap gather form of tn2_wgrad (wgrad.hip).
 //
 // GEMM view over rows m = (n, ho, wo):
 //   fwd:   Y[m, cout] = sum_{tap, cin} X[gather(m, tap), cin] * W[cout, tap, cin]
 //   dgrad: dX[m, cin] = sum_{tap, cout} dY[gather'(m, tap), cout] * W'[cin, tap, cout]
 //          (W' is the 180-degree-rotated, [Cin, 9*Cout]-permuted weight)
-//   wgrad: dW[cout, tap, cin] = sum_m dY[m, cout] * X[gather(m, tap), cin]
-//          (one split-M TN GEMM per tap, atomic fp32 accumulation)
 //
 // Same block structure as gemm.hip (128x128 tile, BK=32 within one tap —
 // all ResNet channel counts are multiples of 32 — 4 waves of 4x4
@@ -41,18 +40,6 @@ __device__ __forceinline__ int xcd_swz(int bid, int nwg) {
 struct ConvGeom {
   int H, W, Hout, Wout, stride;  // input / output spatial dims
 };
-
-// forward gather: output row m=(n,ho,wo), tap (kh,kw) -> input row or -1
-__device__ __forceinline__ long fwd_gather(long m, int kh, int kw,
-                                           const ConvGeom& g) {
-  long t = m;
-  const int wo = (int)(t % g.Wout); t /= g.Wout;
-  const int ho = (int)(t % g.Hout); t /= g.Hout;
-  const int h = ho * g.stride - 1 + kh;
-  const int w = wo * g.stride - 1 + kw;
-  if (h < 0 || h >= g.H || w < 0 || w >= g.W) return -1;
-  return (t * g.H + h) * g.W + w;
-}
 
 // dgrad gather: input row m=(n,h,w), tap (kh,kw) -> dY row or -1
 // (H,W = input dims; Hout,Wout = dY dims)
@@ -384,107 +371,6 @@ conv3x3_kernel(const bf16* __restrict__ A, const bf16* __restrict__ Bw,
                                   bm, wm, wn, fr, fq, As);
 }
 
-// wgrad per tap: dW[cout, tap*Cin + cin] += sum_m dY[m, cout] * Xg[m, cin]
-// Transposed reg-staging + contiguous b128 fragment reads (see gemm.hip
-// gemm_tn); gathered X rows that fall in the padding stage zeros.
-__device__ __forceinline__ int wg_swz(int cc, int m) {
-  return cc * 32 + (m ^ (((((cc >> 3) & 3) ^ ((cc >> 1) & 3))) << 3));
-}
-
-__global__ void __launch_bounds__(GEMM_TPB, 2)
-conv3x3_wgrad_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
-                     float* __restrict__ dW, long M, int Cout, int Cin,
-                     ConvGeom g, int tap, int nbn, int nbk, int msplit) {
-  __shared__ bf16 Ys[128 * 32];
-  __shared__ bf16 Xs[128 * 32];
-
-  const int kh = tap / 3, kw = tap % 3;
-  const int tiles = nbn * nbk;
-  const int tile = blockIdx.x % tiles;
-  const int mpart = blockIdx.x / tiles;
-  const int bn = tile / nbk, bk = tile % nbk;
-  const long n0 = (long)bn * 128, k0 = (long)bk * 128;
-
-  const long mchunks = (M + 31) / 32;
-  const long cpp = (mchunks + msplit - 1) / msplit;
-  const long mc0 = (long)mpart * cpp;
-  const long mc1 = min(mc0 + cpp, mchunks);
-
-  const int t = threadIdx.x;
-  const int wave = t / AMD_WAVE, lane = t % AMD_WAVE;
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  for (long mc = mc0; mc < mc1; ++mc) {
-    const long m0 = mc * 32;
-    __syncthreads();
-#pragma unroll
-    for (int rnd = 0; rnd < 2; ++rnd) {
-      const int unit = rnd * GEMM_TPB + t;  // 16 units (8 cols) per m-row
-      const long m = m0 + (unit >> 4);
-      const int c0 = (unit & 15) * 8;
-      const int mloc = unit >> 4;
-      // dY chunk (cols may exceed Cout for Cout<128 -> zeros)
-      bf16 yv[8];
-      if (m < M && n0 + c0 + 8 <= Cout) {
-        uint4 raw = *(const uint4*)(dY + m * Cout + n0 + c0);
-        __builtin_memcpy(yv, &raw, 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) yv[j] = bf16(0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Ys[wg_swz(c0 + j, mloc)] = yv[j];
-      // gathered X chunk (padding rows and col overflow -> zeros)
-      long xrow = m < M ? fwd_gather(m, kh, kw, g) : -1;
-      bf16 xv[8];
-      if (xrow >= 0 && k0 + c0 + 8 <= Cin) {
-        uint4 raw = *(const uint4*)(X + xrow * (long)Cin + k0 + c0);
-        __builtin_memcpy(xv, &raw, 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xv[j] = bf16(0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Xs[wg_swz(c0 + j, mloc)] = xv[j];
-    }
-    __syncthreads();
-
-    bf16x8 a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      a[i] = *(const bf16x8*)&Ys[wg_swz(wn + i * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      b[j] = *(const bf16x8*)&Xs[wg_swz(wk + j * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a[i], b[j], acc[i][j], 0, 0, 0);
-  }
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long n = n0 + wn + i * 16 + fq * 4 + r;   // cout
-        long k = k0 + wk + j * 16 + fr;           // cin
-        if (n < Cout && k < Cin)
-          atomicAdd(&dW[n * (long)(9 * Cin) + (long)tap * Cin + k],
-                    acc[i][j][r]);
-      }
-}
-
 // permute weight [Cout, 9, Cin] -> [Cin, 9, Cout] for dgrad.
 // NO 180-degree rotation here: the dgrad gather (ho = h+1-kh) already
 // encodes it, so tap k pairs with W[., k, .] directly.
@@ -723,29 +609,4 @@ at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
                                            nullptr, ep);
   CHECK_CUDA_OK();
   return dx;
-}
-
-at::Tensor conv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
-                         long W, long stride) {
-  long Cout = dy2d.size(1), Cin = x2d.size(1);
-  long Hout = (H + 2 - 3) / stride + 1, Wout = (W + 2 - 3) / stride + 1;
-  long M = Nn * Hout * Wout;
-  TORCH_CHECK(dy2d.size(0) == M);
-  auto dW = at::zeros({Cout, 9 * Cin}, dy2d.options().dtype(at::kFloat));
-  ConvGeom g{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride};
-  int nbn = (int)((Cout + 127) / 128), nbk = (int)((Cin + 127) / 128);
-  long tiles = (long)nbn * nbk;
-  const bool det = std::getenv("AMDTRAIN_DETERMINISTIC") != nullptr;
-  int msplit = det ? 1
-                   : (int)std::max<long>(
-                         1, std::min<long>((M + 31) / 32, 512 / tiles));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  for (int tap = 0; tap < 9; ++tap) {
-    conv3x3_wgrad_kernel<<<(int)(tiles * msplit), GEMM_TPB, 0, stream>>>(
-        (const bf16*)dy2d.const_data_ptr(), (const bf16*)x2d.const_data_ptr(),
-        dW.data_ptr<float>(), M, (int)Cout, (int)Cin, g, tap, nbn, nbk,
-        msplit);
-    CHECK_CUDA_OK();
-  }
-  return dW;
 }

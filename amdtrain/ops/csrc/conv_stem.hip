@@ -19,7 +19,7 @@
 // on a 64-wide n-tile, with the BN-statistics partials in the epilogue.
 //
 //   fwd:   Y[m, cout] = sum_col im2col[m, col] * W2[cout, col]
-//   wgrad: dW2[cout, col] = sum_m dY[m, cout] * im2col[m, col]
+//   wgrad: the tap-gather form of tn2_wgrad (wgrad.hip)
 //   dgrad: dX[m=(n,h,w), ci] = sum_col2 im2colT[m, col2] * W2p[ci, col2]
 //          with col2 = tap*Cout + cout, im2colT gathering dY through the
 //          transposed-conv map ho = (h + pad - kh) / stride (exact
@@ -321,120 +321,6 @@ conv_generic_fwd_kernel(const bf16* __restrict__ x,
                                   bm, wm, wn, fr, fq, SMEM);
 }
 
-// wgrad: transposed reg-staging like gemm.hip's gemm_tn, with the B chunk
-// gathered from im2col
-__device__ __forceinline__ int st_swz(int c, int m) {
-  return c * 32 + (m ^ (((((c >> 3) & 3) ^ ((c >> 1) & 3))) << 3));
-}
-
-__global__ void __launch_bounds__(GEMM_TPB, 2)
-conv_generic_wgrad_kernel(const bf16* __restrict__ dY,
-                          const bf16* __restrict__ x, float* __restrict__ dW2,
-                          long M, int Cout, StemGeom g, int nbn, int nbk,
-                          int msplit) {
-  __shared__ bf16 Ys[128 * 32];
-  __shared__ bf16 Xs[128 * 32];
-  const int tiles = nbn * nbk;
-  const int tile = blockIdx.x % tiles;
-  const int mpart = blockIdx.x / tiles;
-  const int bn = tile / nbk, bk = tile % nbk;
-  const long n0 = (long)bn * 128, k0 = (long)bk * 128;
-
-  const long mchunks = (M + 31) / 32;
-  const long cpp = (mchunks + msplit - 1) / msplit;
-  const long mc0 = (long)mpart * cpp;
-  const long mc1 = min(mc0 + cpp, mchunks);
-
-  const int t = threadIdx.x;
-  const int wave = t / AMD_WAVE, lane = t % AMD_WAVE;
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  // col -> (kh, kw, ci) is FIXED per thread across all m-chunks: hoist it
-  const float inv_cin = 1.f / g.Cin, inv_kw = 1.f / g.KW;
-  const int K = g.KH * g.KW * g.Cin;
-  int ckh[2][8], ckw[2][8], cci[2][8];
-  bool cok[2][8];
-#pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
-    const int unit = rnd * GEMM_TPB + t;
-    const int c0 = (unit & 15) * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int col = (int)(k0 + c0 + j);
-      cok[rnd][j] = col < K;
-      col_decode(cok[rnd][j] ? col : 0, g, inv_cin, inv_kw, ckh[rnd][j],
-                 ckw[rnd][j], cci[rnd][j]);
-    }
-  }
-
-  for (long mc = mc0; mc < mc1; ++mc) {
-    const long m0 = mc * 32;
-    __syncthreads();
-#pragma unroll
-    for (int rnd = 0; rnd < 2; ++rnd) {
-      const int unit = rnd * GEMM_TPB + t;
-      const long m = m0 + (unit >> 4);
-      const int c0 = (unit & 15) * 8;
-      const int mloc = unit >> 4;
-      bf16 yv[8];
-      if (m < M && n0 + c0 + 8 <= Cout) {
-        uint4 raw = *(const uint4*)(dY + m * Cout + n0 + c0);
-        __builtin_memcpy(yv, &raw, 16);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) yv[j] = bf16(0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Ys[st_swz(c0 + j, mloc)] = yv[j];
-      bf16 xv[8];
-      StemCoord u = stem_decode(m < M ? m : 0, g);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int h = u.hb + ckh[rnd][j], w = u.wb + ckw[rnd][j];
-        const bool ok = (m < M) && cok[rnd][j] && h >= 0 && h < g.H &&
-                        w >= 0 && w < g.W;
-        long idx = (u.n_off + (long)h * g.W + w) * g.Cin + cci[rnd][j];
-        xv[j] = ok ? x[idx] : bf16(0.f);
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) Xs[st_swz(c0 + j, mloc)] = xv[j];
-    }
-    __syncthreads();
-
-    bf16x8 a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      a[i] = *(const bf16x8*)&Ys[st_swz(wn + i * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      b[j] = *(const bf16x8*)&Xs[st_swz(wk + j * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a[i], b[j], acc[i][j], 0, 0, 0);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long n = n0 + wn + i * 16 + fq * 4 + r;
-        long k = k0 + wk + j * 16 + fr;
-        if (n < Cout && k < g.Kpad)
-          atomicAdd(&dW2[n * (long)g.Kpad + k], acc[i][j][r]);
-      }
-}
-
 // stride_w == 0 / pad_w < 0 / Hout, Wout == 0: same as along h / symmetric
 // padding.  Explicit output dims serve asymmetric padding (only the top /
 // left amounts enter the gather; the bottom / right are implied).
@@ -611,26 +497,4 @@ at::Tensor conv_generic_dgrad(at::Tensor dy2d, at::Tensor w2p, long Nn,
         0);
   CHECK_CUDA_OK();
   return dx;
-}
-
-at::Tensor conv_generic_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn,
-                              long H, long W, long KH, long KW, long stride,
-                              long pad) {
-  long Cin = x2d.size(1), Cout = dy2d.size(1);
-  auto g = make_geom(H, W, KH, KW, Cin, stride, pad);
-  long M = Nn * g.Hout * g.Wout;
-  TORCH_CHECK(dy2d.size(0) == M);
-  auto dW2 = at::zeros({Cout, g.Kpad}, dy2d.options().dtype(at::kFloat));
-  int nbn = (int)((Cout + 127) / 128), nbk = (int)((g.Kpad + 127) / 128);
-  long tiles = (long)nbn * nbk;
-  const bool det = std::getenv("AMDTRAIN_DETERMINISTIC") != nullptr;
-  int msplit = det ? 1
-                   : (int)std::max<long>(
-                         1, std::min<long>((M + 31) / 32, 512 / tiles));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  conv_generic_wgrad_kernel<<<(int)(tiles * msplit), GEMM_TPB, 0, stream>>>(
-      (const bf16*)dy2d.const_data_ptr(), (const bf16*)x2d.const_data_ptr(),
-      dW2.data_ptr<float>(), M, (int)Cout, g, nbn, nbk, msplit);
-  CHECK_CUDA_OK();
-  return dW2;
 }

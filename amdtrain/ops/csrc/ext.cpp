@@ -75,11 +75,9 @@ std::vector<at::Tensor> batch_norm_bwd_pool(
 at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
                    std::optional<at::Tensor> addend,
                    std::optional<at::Tensor> bias, long epi);
-at::Tensor gemm_tn(at::Tensor dY, at::Tensor X, long msplit);
 at::Tensor gemm_bt_strided(at::Tensor A, at::Tensor B, long Nn, long H,
                            long W, long stride, long epi);
-at::Tensor gemm_tn_strided(at::Tensor dY, at::Tensor X, long Nn, long H,
-                           long W, long stride);
+std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B, long epi);
 at::Tensor transpose_2d(at::Tensor x);
 
 // conv3x3.hip
@@ -89,18 +87,12 @@ std::vector<at::Tensor> conv3x3_fwd_stats(at::Tensor x2d, long Nn, long H,
                                           long W, long stride,
                                           at::Tensor w2d, bool banded,
                                           bool nt64, long epi);
-std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B, long epi);
-
-// gemm8p.hip
-at::Tensor gemm_bt_8p(at::Tensor A, at::Tensor B);
-at::Tensor gemm_bt_8p3(at::Tensor A, at::Tensor B);
-at::Tensor conv3x3_8p(at::Tensor A2d, long Nn, long H, long W, long stride,
-                      at::Tensor w2d, bool dgrad);
 at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
                          long stride, at::Tensor w2d, bool banded,
                          bool s2parity, bool nt64, long epi);
-at::Tensor conv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
-                         long W, long stride);
+
+// gemm8p.hip
+at::Tensor gemm_bt_8p3(at::Tensor A, at::Tensor B);
 
 // wgrad.hip
 at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
@@ -120,9 +112,6 @@ std::vector<at::Tensor> conv_generic_fwd_stats(
     at::Tensor x2d, long Nn, long H, long W, long KH, long KW, long stride,
     long pad, at::Tensor w2, long stride_w, long pad_w, long Hout, long Wout,
     bool tile64, long epi);
-at::Tensor conv_generic_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn,
-                              long H, long W, long KH, long KW, long stride,
-                              long pad);
 at::Tensor conv_generic_dgrad(at::Tensor dy2d, at::Tensor w2p, long Nn,
                               long H, long W, long KH, long KW, long stride,
                               long pad);
@@ -186,12 +175,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bt", &gemm_bt, py::arg("A"), py::arg("B"),
         py::arg("f32_out") = false, py::arg("addend") = std::nullopt,
         py::arg("bias") = std::nullopt, py::arg("epi") = -1);
-  m.def("gemm_tn", &gemm_tn, py::arg("dY"), py::arg("X"),
-        py::arg("msplit") = 0);
   m.def("gemm_bt_strided", &gemm_bt_strided, py::arg("A"), py::arg("B"),
         py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("stride"),
         py::arg("epi") = -1);
-  m.def("gemm_tn_strided", &gemm_tn_strided);
   m.def("transpose_2d", &transpose_2d);
   m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
@@ -202,14 +188,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("epi") = -1);
   m.def("gemm_bt_stats", &gemm_bt_stats, py::arg("A"), py::arg("B"),
         py::arg("epi") = -1);
-  m.def("gemm_bt_8p", &gemm_bt_8p);
   m.def("gemm_bt_8p3", &gemm_bt_8p3);
-  m.def("conv3x3_8p", &conv3x3_8p);
   m.def("conv3x3_dgrad", &conv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
         py::arg("banded") = false, py::arg("s2parity") = true,
         py::arg("nt64") = true, py::arg("epi") = -1);
-  m.def("conv3x3_wgrad", &conv3x3_wgrad);
   m.def("tn2_wgrad", &tn2_wgrad, py::arg("dY"), py::arg("X"),
         py::arg("taps") = 1, py::arg("Nn") = 0, py::arg("H") = 0,
         py::arg("W") = 0, py::arg("stride") = 1, py::arg("gmode") = 0,
@@ -230,7 +213,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride_w") = 0, py::arg("pad_w") = -1, py::arg("Hout") = 0,
         py::arg("Wout") = 0, py::arg("tile64") = false,
         py::arg("epi") = -1);
-  m.def("conv_generic_wgrad", &conv_generic_wgrad);
   m.def("conv_generic_dgrad", &conv_generic_dgrad);
   m.def("max_pool_3x3_s2_fwd", &max_pool_3x3_s2_fwd, py::arg("x"),
         py::arg("scale") = std::nullopt, py::arg("shift") = std::nullopt);

@@ -13,8 +13,8 @@
 //   gemm_bt:  C[M,N] = A[M,K] x B[N,K]^T  (bf16 in, bf16 or f32 out)
 //             -> conv1x1 forward (A = NHWC activation rows, B = weight)
 //             -> conv1x1 dgrad   (A = grad rows, B = pre-transposed weight)
-//   gemm_tn:  C[N,K] += A[M,N]^T x B[M,K]  (f32 accumulation via split-M
-//             atomics) -> conv1x1 wgrad
+//   gemm_bt_stats:   gemm_bt + per-block BN (sum, sumsq) partials
+//   gemm_bt_strided: gemm_bt over the strided 1x1-conv row gather
 //   transpose_2d: bf16 [N,K] -> [K,N] (per-step weight transpose for dgrad)
 #include "common.h"
 
@@ -90,14 +90,6 @@ __device__ __forceinline__ void stage_tile_rows(
 // helps) -> ON by default for K <= GEMM_DB_KMAX, AMDTRAIN_GEMM_DB=0/1
 // forces either path.
 constexpr long GEMM_DB_KMAX = 1024;
-// AMDTRAIN_GEMM_ADIR=1: opt-in direct-from-global A fragments (see kernel)
-inline bool gemm_adir_enabled() {
-  static const bool v = []() {
-    const char* e = std::getenv("AMDTRAIN_GEMM_ADIR");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
 inline bool gemm_db_enabled(long K) {
   static const int v = []() {
     const char* e = std::getenv("AMDTRAIN_GEMM_DB");
@@ -183,36 +175,22 @@ __device__ __forceinline__ void epilogue_stats(
   }
 }
 
-// NT: nontemporal C stores (global_store_* nt) — A/B experiment for the
-// ~4.2 TB/s streaming wall on the BW-bound shapes (AMDTRAIN_GEMM_NT=1)
-// NT=1: nontemporal C stores — measured 2x SLOWER (breaks write combining
-// of the 2 B scattered stores); kept env-gated as a documented negative.
-// LDSE=1: stage the C tile through LDS and emit coalesced 16 B stores
-// instead of per-element column-strided 2 B stores.
 // DB=1: double-buffered K-loop — stage chunk kt+1 while the MFMAs consume
 // chunk kt (one barrier per chunk instead of two, per-block load/compute
 // overlap instead of relying on the 2-blocks/CU interleave drifting into
 // opposite phase).  The barrier's implicit vmcnt(0) wait is what drains
 // the global_load_lds queue, exactly as in the single-buffer path.
-// ADIR=1: A fragments are read DIRECTLY from global memory into VGPRs —
-// the mfma A fragment is 16 contiguous bytes of one A row (lane l reads
-// A[row=l&15][k=(l>>4)*8..+7]), so no LDS transit is needed at all: the
-// A-side DMA and half the LDS footprint disappear; the second wave on
-// the same rows hits L1.  A/B experiment for the streaming shapes
-// (AMDTRAIN_GEMM_ADIR).  Plain (non-strided, non-LDSE) path only.
 // WIDE: the wide-store C epilogue and its B-row map (common.h); epi is the
 // runtime epilogue mode of the narrow one (AMDTRAIN_EPILOGUE 0 / 1).
-template <bool F32OUT, bool STRIDED, bool NT = false, bool LDSE = false,
-          bool DB = false, bool ADIR = false, bool WIDE = false>
+template <bool F32OUT, bool STRIDED, bool DB = false, bool WIDE = false>
 __global__ void __launch_bounds__(GEMM_TPB, 2)
 gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                void* __restrict__ C, long M, long N, long K, int nbm,
                int nbn, StrideMap sm, float* __restrict__ stats, int epi) {
-  static_assert(!WIDE || !(F32OUT || NT || LDSE), "WIDE is a bf16 epilogue");
-  __shared__ bf16 SMEM[(DB ? 2 : 1) *
-                       ((ADIR ? 0 : BM) + BN) * BK];  // [As |] Bs
-  bf16* const As = SMEM;    // (contiguous: the LDSE epilogue reuses 16 KB)
-  bf16* const Bs = SMEM + (ADIR ? 0 : BM * BK);
+  static_assert(!WIDE || !F32OUT, "WIDE is a bf16 epilogue");
+  __shared__ bf16 SMEM[(DB ? 2 : 1) * (BM + BN) * BK];  // As | Bs
+  bf16* const As = SMEM;
+  bf16* const Bs = SMEM + BM * BK;
 
   const int nwg = nbm * nbn;
   const int bid = xcd_swizzle(blockIdx.x, nwg);
@@ -243,34 +221,20 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
     }
   }
 
-  // ADIR: per-lane clamped global row pointers for the 4 A fragments
-  const bf16* Ap[4];
-  if (ADIR) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      long row = m0 + wm + i * 16 + fr;
-      if (row >= M) row = M - 1;  // finite garbage, epilogue masks it
-      Ap[i] = A + row * K + fq * 8;
-    }
-  }
   const long ksteps = K / BK;
   auto stage = [&](long kt, bf16* as) {
-    if (!ADIR) {
-      if (STRIDED)
-        stage_tile_rows(A, K, arow, kt * BK, as);
-      else
-        stage_tile_128x32(A, K, m0, M, kt * BK, as);
-    }
-    stage_tile_128x32(B, K, n0, N, kt * BK,
-                      as + (ADIR ? 0 : BM * BK));
+    if (STRIDED)
+      stage_tile_rows(A, K, arow, kt * BK, as);
+    else
+      stage_tile_128x32(A, K, m0, M, kt * BK, as);
+    stage_tile_128x32(B, K, n0, N, kt * BK, as + BM * BK);
   };
-  auto compute = [&](const bf16* as, long kt) {
-    const bf16* bs = as + (ADIR ? 0 : BM * BK);
+  auto compute = [&](const bf16* as) {
+    const bf16* bs = as + BM * BK;
     bf16x8 a[4], b[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      a[i] = ADIR ? *(const bf16x8*)(Ap[i] + kt * BK)
-                  : *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
+      a[i] = *(const bf16x8*)&as[(wm + i * 16 + fr) * BK + fq * 8];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       b[j] = *(const bf16x8*)
@@ -283,7 +247,7 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
             a[i], b[j], acc[i][j], 0, 0, 0);
   };
   if (DB) {
-    constexpr int HB = ((ADIR ? 0 : BM) + BN) * BK;
+    constexpr int HB = (BM + BN) * BK;
     if (ksteps > 0) stage(0, SMEM);
     for (long kt = 0; kt < ksteps; ++kt) {
       bf16* const as = SMEM + (kt & 1) * HB;
@@ -291,45 +255,19 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                         // vmcnt(0)); all waves are past reading the
                         // other buffer, which kt+1 overwrites below
       if (kt + 1 < ksteps) stage(kt + 1, SMEM + ((kt + 1) & 1) * HB);
-      compute(as, kt);
+      compute(as);
     }
   } else {
     for (long kt = 0; kt < ksteps; ++kt) {
       __syncthreads();  // previous compute done before overwriting LDS
       stage(kt, SMEM);
       __syncthreads();  // barrier drains the global_load_lds queue
-      compute(SMEM, kt);
+      compute(SMEM);
     }
   }
 
   // epilogue: C[m0+wm+i*16+fq*4+r][n0+wn+j*16+fr]
-  if (LDSE && !F32OUT && n0 + 128 <= N) {
-    // stage the bf16 C tile through LDS (reusing the 16 KB staging buffer,
-    // 64 rows per round) and emit coalesced 16 B row-major stores instead
-    // of the fragment-shaped column-strided 2 B stores
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      __syncthreads();
-      if (wm == h * 64) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              SMEM[(i * 16 + fq * 4 + r) * 128 + wn + j * 16 + fr] =
-                  __float2bfloat16(acc[i][j][r]);
-      }
-      __syncthreads();
-      for (int u2 = t; u2 < 1024; u2 += GEMM_TPB) {
-        const int row_l = u2 >> 3;
-        const long row = m0 + h * 64 + row_l;
-        if (row < M)
-          *(uint4*)((bf16*)C + row * N + n0 + (u2 & 7) * 16) =
-              ((const uint4*)SMEM)[u2];
-      }
-    }
-  } else if (F32OUT || NT) {
+  if (F32OUT) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -338,16 +276,7 @@ gemm_bt_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
         for (int r = 0; r < 4; ++r) {
           long row = m0 + wm + i * 16 + fq * 4 + r;
           long col = n0 + wn + j * 16 + fr;
-          if (row < M && col < N) {
-            if (F32OUT) {
-              ((float*)C)[row * N + col] = acc[i][j][r];
-            } else {
-              bf16 v = __float2bfloat16(acc[i][j][r]);
-              short b;
-              __builtin_memcpy(&b, &v, 2);
-              __builtin_nontemporal_store(b, (short*)C + row * N + col);
-            }
-          }
+          if (row < M && col < N) ((float*)C)[row * N + col] = acc[i][j][r];
         }
       }
     }
@@ -551,148 +480,6 @@ gemm_ks_collapse_kernel(const float* __restrict__ parts,
   }
 }
 
-// ---- TN GEMM for wgrad: dW[N,K] += sum_m dY[m,n] * X[m,k] ----------------
-// Output tiles 128n x 128k, M chunked by 32 and split across blocks
-// (split-M) with fp32 atomic accumulation into dW.
-//
-// The MFMA fragments need the m-major (transposed) view of both chunks, so
-// staging is global->reg->TRANSPOSED LDS write ([col][32 m] layout with an
-// 8-element-block XOR swizzle to spread write banks); fragment loads are
-// then contiguous ds_read_b128.  Out-of-range rows/cols stage zeros, which
-// also removes per-fragment masking.
-__device__ __forceinline__ int tn_swz(int c, int m) {
-  // XOR c-bits 1-2 as well: spreads the stride-1 fragment reads over
-  // 8 banks (2-way, free) while keeping the stride-8 writes at 4-way
-  return c * 32 + (m ^ (((((c >> 3) & 3) ^ ((c >> 1) & 3))) << 3));
-}
-
-// stage a [32 m][128 col] chunk of a [M x ld] matrix, transposed, into LDS
-__device__ __forceinline__ void tn_stage(const bf16* __restrict__ g, long ld,
-                                         long m0, long M, long col0,
-                                         bf16* lds) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
-    const int unit = rnd * GEMM_TPB + t;  // 16 units (of 8 cols) per m-row
-    const long m = m0 + (unit >> 4);
-    const int c0 = (unit & 15) * 8;
-    bf16 vals[8];
-    if (m < M && col0 + c0 + 8 <= ld) {
-      uint4 raw = *(const uint4*)(g + m * ld + col0 + c0);
-      __builtin_memcpy(vals, &raw, 16);
-    } else if (m < M && col0 + c0 < ld) {  // ragged col tail
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        vals[j] = (col0 + c0 + j < ld) ? g[m * ld + col0 + c0 + j]
-                                       : bf16(0.f);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vals[j] = bf16(0.f);
-    }
-    const int mloc = unit >> 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lds[tn_swz(c0 + j, mloc)] = vals[j];
-  }
-}
-
-// tn_stage over strided-gathered rows (row = stride_row(m))
-__device__ __forceinline__ void tn_stage_strided(
-    const bf16* __restrict__ g, long ld, long m0, long M, long col0,
-    const StrideMap& sm, bf16* lds) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
-    const int unit = rnd * GEMM_TPB + t;
-    const long m = m0 + (unit >> 4);
-    const int c0 = (unit & 15) * 8;
-    bf16 vals[8];
-    if (m < M && col0 + c0 + 8 <= ld) {
-      const long row = stride_row(m, sm);
-      uint4 raw = *(const uint4*)(g + row * ld + col0 + c0);
-      __builtin_memcpy(vals, &raw, 16);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vals[j] = bf16(0.f);
-    }
-    const int mloc = unit >> 4;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) lds[tn_swz(c0 + j, mloc)] = vals[j];
-  }
-}
-
-template <bool STRIDED>
-__global__ void __launch_bounds__(GEMM_TPB, 2)
-gemm_tn_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
-               float* __restrict__ dW, long M, long N, long K, int nbn,
-               int nbk, int msplit, StrideMap sm) {
-  __shared__ bf16 Ys[128 * 32];
-  __shared__ bf16 Xs[128 * 32];
-
-  const int tiles = nbn * nbk;
-  const int tile = blockIdx.x % tiles;
-  const int mpart = blockIdx.x / tiles;
-  const int bn = tile / nbk, bk = tile % nbk;
-  const long n0 = (long)bn * BM, k0 = (long)bk * BN;
-
-  const long mchunks = (M + 31) / 32;
-  const long chunks_per_part = (mchunks + msplit - 1) / msplit;
-  const long mc0 = (long)mpart * chunks_per_part;
-  const long mc1 = min(mc0 + chunks_per_part, mchunks);
-
-  const int t = threadIdx.x;
-  const int wave = t / AMD_WAVE;
-  const int lane = t % AMD_WAVE;
-  const int wn = (wave >> 1) * 64;
-  const int wk = (wave & 1) * 64;
-  const int fr = lane & 15;
-  const int fq = lane >> 4;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  for (long mc = mc0; mc < mc1; ++mc) {
-    const long m0 = mc * 32;
-    __syncthreads();
-    tn_stage(dY, N, m0, M, n0, Ys);
-    if (STRIDED)
-      tn_stage_strided(X, K, m0, M, k0, sm, Xs);
-    else
-      tn_stage(X, K, m0, M, k0, Xs);
-    __syncthreads();
-
-    // A fragment: dY^T[n][m]; B fragment: X^T -> both contiguous b128 reads
-    bf16x8 a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      a[i] = *(const bf16x8*)&Ys[tn_swz(wn + i * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      b[j] = *(const bf16x8*)&Xs[tn_swz(wk + j * 16 + fr, fq * 8)];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            a[i], b[j], acc[i][j], 0, 0, 0);
-  }
-
-  // atomic split-M accumulation (measured cheaper than a partial-buffer
-  // second pass, whose traffic scales with block count)
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long n = n0 + wn + i * 16 + fq * 4 + r;
-        long k = k0 + wk + j * 16 + fr;
-        if (n < N && k < K) atomicAdd(&dW[n * K + k], acc[i][j][r]);
-      }
-}
-
 // ---- small bf16 2D transpose (per-step weight transpose for dgrad) -------
 __global__ void __launch_bounds__(AMD_TPB)
 transpose_2d_kernel(const bf16* __restrict__ in, bf16* __restrict__ out,
@@ -735,7 +522,7 @@ static void launch_bt(bool db, bool wide, int grid, hipStream_t stream,
                       long K, int nbm, int nbn, const StrideMap& sm,
                       float* stats, int epi) {
 #define AMDTRAIN_BT(DBV, WV)                                                \
-  gemm_bt_kernel<false, STRIDED, false, false, DBV, false, WV>              \
+  gemm_bt_kernel<false, STRIDED, DBV, WV>                                   \
       <<<grid, GEMM_TPB, 0, stream>>>(A, B, C, M, N, K, nbm, nbn, sm,       \
                                       stats, epi)
   if (db && wide) AMDTRAIN_BT(true, true);
@@ -820,31 +607,12 @@ at::Tensor gemm_bt(at::Tensor A, at::Tensor B, bool f32_out,
     CHECK_CUDA_OK();
     return C;
   }
-  static const bool use_nt = []() {
-    const char* v = std::getenv("AMDTRAIN_GEMM_NT");
-    return v && v[0] == '1';
-  }();
   const bool use_db = gemm_db_enabled(K);
-  static const bool use_ldse = []() {
-    const char* v = std::getenv("AMDTRAIN_GEMM_LDSE");
-    return v && v[0] == '1';
-  }();
   const int grid = nbm * nbn, ep = epi_mode(epi, EPI_DEFAULT_BT);
   const bool wide = epi_wide(ep, N);
   if (f32_out)
     gemm_bt_kernel<true, false><<<grid, GEMM_TPB, 0, stream>>>(
         Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr, ep);
-  else if (use_ldse && N % 8 == 0)
-    gemm_bt_kernel<false, false, false, true>
-        <<<grid, GEMM_TPB, 0, stream>>>(Ap, Bp, C.data_ptr(), M, N, K, nbm,
-                                        nbn, sm, nullptr, ep);
-  else if (use_nt)
-    gemm_bt_kernel<false, false, true><<<grid, GEMM_TPB, 0, stream>>>(
-        Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm, nullptr, ep);
-  else if (gemm_adir_enabled())
-    gemm_bt_kernel<false, false, false, false, true, true>
-        <<<grid, GEMM_TPB, 0, stream>>>(Ap, Bp, C.data_ptr(), M, N, K, nbm,
-                                        nbn, sm, nullptr, ep);
   else
     launch_bt<false>(use_db, wide, grid, stream, Ap, Bp, C.data_ptr(), M, N,
                      K, nbm, nbn, sm, nullptr, ep);
@@ -879,11 +647,6 @@ std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B, long epi) {
     launch_bt_n2(use_db, epi_wide(ep2, N), nbm * nbn2, stream, Ap, Bp,
                  (bf16*)C.data_ptr(), M, N, K, nbm, nbn2,
                  stats.data_ptr<float>(), ep2);
-  } else if (gemm_adir_enabled()) {
-    gemm_bt_kernel<false, false, false, false, true, true>
-        <<<nbm * nbn, GEMM_TPB, 0, stream>>>(
-            Ap, Bp, C.data_ptr(), M, N, K, nbm, nbn, sm,
-            stats.data_ptr<float>(), ep);
   } else {
     launch_bt<false>(use_db, epi_wide(ep, N), nbm * nbn, stream, Ap, Bp,
                      C.data_ptr(), M, N, K, nbm, nbn, sm,
@@ -917,56 +680,6 @@ at::Tensor gemm_bt_strided(at::Tensor A, at::Tensor B, long Nn, long H,
                   nbm, nbn, sm, nullptr, ep);
   CHECK_CUDA_OK();
   return C;
-}
-
-at::Tensor gemm_tn(at::Tensor dY, at::Tensor X, long msplit) {
-  TORCH_CHECK(dY.is_cuda() && dY.dim() == 2 && X.dim() == 2);
-  TORCH_CHECK(dY.scalar_type() == at::kBFloat16 &&
-              X.scalar_type() == at::kBFloat16);
-  auto Yc = dY.contiguous();
-  auto Xc = X.contiguous();
-  long M = Yc.size(0), N = Yc.size(1), K = Xc.size(1);
-  TORCH_CHECK(Xc.size(0) == M, "M mismatch");
-  TORCH_CHECK(N % 8 == 0 && K % 8 == 0, "N,K must be multiples of 8");
-  auto dW = at::zeros({N, K}, Yc.options().dtype(at::kFloat));
-  int nbn = (int)((N + 127) / 128), nbk = (int)((K + 127) / 128);
-  long tiles = (long)nbn * nbk;
-  const bool det = std::getenv("AMDTRAIN_DETERMINISTIC") != nullptr;
-  if (det)
-    msplit = 1;  // single-accumulator: bitwise-deterministic wgrad
-  else if (msplit <= 0)
-    msplit = std::max<long>(1, std::min<long>((M + 31) / 32, 512 / tiles));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  StrideMap sm{0, 0, 0, 0, 1};
-  gemm_tn_kernel<false><<<(int)(tiles * msplit), GEMM_TPB, 0, stream>>>(
-      (const bf16*)Yc.const_data_ptr(), (const bf16*)Xc.const_data_ptr(),
-      dW.data_ptr<float>(), M, N, K, nbn, nbk, (int)msplit, sm);
-  CHECK_CUDA_OK();
-  return dW;
-}
-
-// wgrad of the strided 1x1 conv: X rows gathered in-kernel
-at::Tensor gemm_tn_strided(at::Tensor dY, at::Tensor X, long Nn, long H,
-                           long W, long stride) {
-  auto Yc = dY.contiguous();
-  auto Xc = X.contiguous();
-  long M = Yc.size(0), N = Yc.size(1), K = Xc.size(1);
-  TORCH_CHECK(N % 8 == 0 && K % 8 == 0);
-  long Hout = (H + stride - 1) / stride, Wout = (W + stride - 1) / stride;
-  TORCH_CHECK(M == Nn * Hout * Wout, "M mismatch for strided wgrad");
-  auto dW = at::zeros({N, K}, Yc.options().dtype(at::kFloat));
-  int nbn = (int)((N + 127) / 128), nbk = (int)((K + 127) / 128);
-  long tiles = (long)nbn * nbk;
-  const bool det2 = std::getenv("AMDTRAIN_DETERMINISTIC") != nullptr;
-  long msplit = det2 ? 1 : std::max<long>(
-      1, std::min<long>((M + 31) / 32, 512 / tiles));
-  StrideMap sm{(int)H, (int)W, (int)Hout, (int)Wout, (int)stride};
-  auto stream = at::cuda::getCurrentCUDAStream();
-  gemm_tn_kernel<true><<<(int)(tiles * msplit), GEMM_TPB, 0, stream>>>(
-      (const bf16*)Yc.const_data_ptr(), (const bf16*)Xc.const_data_ptr(),
-      dW.data_ptr<float>(), M, N, K, nbn, nbk, (int)msplit, sm);
-  CHECK_CUDA_OK();
-  return dW;
 }
 
 at::Tensor transpose_2d(at::Tensor x) {

@@ -4,13 +4,14 @@
 // (SURVEY §2c rows "Linear/GEMM (cuBLAS)" wgrad + "Conv2d 3x3" wgrad;
 // reference hot path /root/reference/distributed.py:268 loss.backward()).
 //
-// Why v2 (round-1 profile: conv3x3_wgrad 19 ms/step + gemm_tn 10 ms/step):
+// Why v2 (round-1 profile: conv3x3 wgrad 19 ms/step + 1x1 wgrad 10 ms/step;
+// those kernels are gone, docs/KERNELS.md keeps the record):
 //  * the round-1 TN kernels transposed through REGISTERS with per-element
 //    swizzled ds_write_b16 (32 x 2B writes per thread per 32-m chunk) and
 //    drained two barriers per chunk for only 16 MFMA/wave;
 //  * conv3x3 wgrad launched 9 separate kernels re-reading dY and X per tap;
-//  * split-M accumulated through fp32 atomicAdd — heavily contended on the
-//    small early-layer dW tiles.
+//  * split-M accumulated through fp32 atomic adds — heavily contended on
+//    the small early-layer dW tiles.
 // v2 fixes all three:
 //  * staging is __builtin_amdgcn_global_load_lds DIRECT into a subtiled
 //    layout consumed by ds_read_b64_tr_b16 (gfx950 hardware transpose read,
@@ -22,8 +23,7 @@
 //    per chunk, 32 MFMA/wave between barriers (MC=64);
 //  * split-M partial outputs go to a [msplit, N*K] fp32 buffer with plain
 //    stores + a vectorized collapse kernel — no atomics, and the reduction
-//    order is FIXED, so wgrad v2 is bitwise deterministic by construction
-//    (no AMDTRAIN_DETERMINISTIC slow path needed).
+//    order is FIXED, so wgrad v2 is bitwise deterministic by construction.
 //
 // LDS layout ("tr-subtile", derived from the guide's m156 mapping): the
 // [MC x NCOLS] operand tile is stored as 256-element (512 B) groups
@@ -569,6 +569,30 @@ __global__ void tr16_probe_kernel(const short* __restrict__ in,
   }
 }
 
+// Sum the msplit partials [msplit, NK] into out [NK] in a fixed order: one
+// pass, or for large msplit a fold to TN2_FOLD rows and a pass over those.
+static void tn2_collapse(const at::Tensor& parts, at::Tensor& out, int msplit,
+                         long NK, hipStream_t stream) {
+  TORCH_CHECK(NK % 4 == 0);
+  const int nkgrid = amd_grid(NK / 4);
+  if (msplit > 2 * TN2_FOLD) {
+    auto folded = at::empty({TN2_FOLD, NK}, out.options());
+    tn2_collapse_kernel<<<nkgrid * TN2_FOLD, AMD_TPB, 0, stream>>>(
+        (const float*)parts.const_data_ptr(), folded.data_ptr<float>(),
+        msplit, TN2_FOLD, NK);
+    CHECK_CUDA_OK();
+    tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
+        (const float*)folded.const_data_ptr(), out.data_ptr<float>(),
+        TN2_FOLD, 1, NK);
+    CHECK_CUDA_OK();
+  } else {
+    tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
+        (const float*)parts.const_data_ptr(), out.data_ptr<float>(), msplit,
+        1, NK);
+    CHECK_CUDA_OK();
+  }
+}
+
 static at::Tensor tn2_zero_page(const at::Tensor& like) {
   static thread_local at::Tensor zp;
   if (!zp.defined() || zp.device() != like.device())
@@ -650,27 +674,7 @@ void tn2_launch(const at::Tensor& dY, const at::Tensor& X, at::Tensor& out,
     launch(tn2_kernel<GMODE, NW, KW, MC, NBUF>);
   }
   CHECK_CUDA_OK();
-  if (msplit > 1) {
-    const long NK = (long)N * K9;
-    TORCH_CHECK(NK % 4 == 0);
-    const int nkgrid = amd_grid(NK / 4);
-    if (msplit > 2 * TN2_FOLD) {
-      auto folded = at::empty({TN2_FOLD, NK}, out.options());
-      tn2_collapse_kernel<<<nkgrid * TN2_FOLD, AMD_TPB, 0, stream>>>(
-          (const float*)parts.const_data_ptr(), folded.data_ptr<float>(),
-          msplit, TN2_FOLD, NK);
-      CHECK_CUDA_OK();
-      tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
-          (const float*)folded.const_data_ptr(), out.data_ptr<float>(),
-          TN2_FOLD, 1, NK);
-      CHECK_CUDA_OK();
-    } else {
-      tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
-          (const float*)parts.const_data_ptr(), out.data_ptr<float>(), msplit,
-          1, NK);
-      CHECK_CUDA_OK();
-    }
-  }
+  if (msplit > 1) tn2_collapse(parts, out, msplit, (long)N * K9, stream);
 }
 
 }  // namespace
@@ -692,7 +696,9 @@ at::Tensor tn2_wgrad(at::Tensor dY, at::Tensor X, long taps, long Nn, long H,
   const int N = (int)Yc.size(1);
   const int Cin = (int)Xc.size(1);
   const int K9 = (int)(taps * Cin);
-  TORCH_CHECK(Cin % 8 == 0 && N % 8 == 0);
+  TORCH_CHECK(Cin % 8 == 0 && N % 8 == 0,
+              "tn2_wgrad needs dY columns (Cout) and X columns (Cin) that are "
+              "multiples of 8, got Cout = ", N, ", Cin = ", Cin);
   TnGeom geo{0, 0, 0, 0, 1, 3, 3, 1, 1, 1};
   if (gmode == 1) {
     long Hout = (H + stride - 1) / stride, Wout = (W + stride - 1) / stride;
@@ -836,26 +842,8 @@ at::Tensor tn2_wgrad_banded(at::Tensor dY, at::Tensor X, long Nn, long H,
   else
     launch(tn2_kernel<2, 2, 2, 64, 2, true>);
   CHECK_CUDA_OK();
-  if (msplit > 1) {
-    const long NK = (long)N * 9 * 128;
-    const int nkgrid = amd_grid(NK / 4);
-    if (msplit > 2 * TN2_FOLD) {
-      auto folded = at::empty({TN2_FOLD, NK}, out.options());
-      tn2_collapse_kernel<<<nkgrid * TN2_FOLD, AMD_TPB, 0, stream>>>(
-          (const float*)parts.const_data_ptr(), folded.data_ptr<float>(),
-          msplit, TN2_FOLD, NK);
-      CHECK_CUDA_OK();
-      tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
-          (const float*)folded.const_data_ptr(), out.data_ptr<float>(),
-          TN2_FOLD, 1, NK);
-      CHECK_CUDA_OK();
-    } else {
-      tn2_collapse_kernel<<<nkgrid, AMD_TPB, 0, stream>>>(
-          (const float*)parts.const_data_ptr(), out.data_ptr<float>(),
-          msplit, 1, NK);
-      CHECK_CUDA_OK();
-    }
-  }
+  if (msplit > 1)
+    tn2_collapse(parts, out, msplit, (long)N * 9 * 128, stream);
   return out;
 }
 

@@ -320,9 +320,8 @@ def test_training_bitwise_deterministic():
     """Two identical 3-step trainings must produce BITWISE-identical
     parameters: every kernel on the path (conv fwd/dgrad, tn2 wgrads,
     BN with fixed-order collapses, fused SGD, CE) has a fixed reduction
-    order — no atomics anywhere in the default path (SURVEY §5
-    determinism; the r1 design needed AMDTRAIN_DETERMINISTIC, r2 does
-    not)."""
+    order — no atomics anywhere in the extension (SURVEY §5
+    determinism)."""
     from amdtrain.models import build_model
     from amdtrain.ops import CrossEntropyLoss, FusedSGD
 

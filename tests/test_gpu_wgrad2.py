@@ -113,21 +113,28 @@ def test_tn2_conv3x3_vs_ref(cfg):
         (dw4 - wref).abs().max().item()
 
 
-def test_tn2_matches_old_kernels():
-    """v2 against the round-1 kernels on a ResNet-50 shape of each family."""
+def test_tn2_resnet50_shapes_vs_ref():
+    """tn2_wgrad against fp32 references on a ResNet-50 shape of each
+    family.  Both sides sum exact bf16 products in fp32."""
     e = _ext()
     torch.manual_seed(2)
     # plain 1x1
     dY = torch.randn(6272, 256, device=DEV).bfloat16()
     X = torch.randn(6272, 64, device=DEV).bfloat16()
     new = e.tn2_wgrad(dY, X)
-    old = e.gemm_tn(dY, X, 0)
-    assert torch.allclose(new, old, atol=0.5, rtol=0.01)
+    ref = dY.float().t() @ X.float()
+    assert torch.allclose(new, ref, atol=0.5, rtol=0.01), \
+        (new - ref).abs().max().item()
     # conv3x3
     n, cin, cout, hw = 4, 128, 128, 28
     x2d = torch.randn(n * hw * hw, cin, device=DEV).bfloat16()
     gy2d = torch.randn(n * hw * hw, cout, device=DEV).bfloat16()
     new = e.tn2_wgrad(gy2d, x2d, 9, n, hw, hw, 1, 2)
-    old = e.conv3x3_wgrad(gy2d, x2d, n, hw, hw, 1)
-    assert torch.allclose(new, old, atol=0.5, rtol=0.01), \
-        (new - old).abs().max().item()
+    x = x2d.float().view(n, hw, hw, cin).permute(0, 3, 1, 2)
+    gy = gy2d.float().view(n, hw, hw, cout).permute(0, 3, 1, 2)
+    wref = torch.nn.grad.conv2d_weight(
+        x, (cout, cin, 3, 3), gy, stride=1, padding=1)
+    # [Cout, Cin, 3, 3] -> [Cout, 9*Cin] (tap-major columns)
+    ref = wref.permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+    assert torch.allclose(new, ref, atol=0.5, rtol=0.01), \
+        (new - ref).abs().max().item()

@@ -1,5 +1,6 @@
-"""Micro-benchmark: gemm_bt (128x128 m97 structure) vs gemm_bt_8p (256x256)
-on square + ResNet conv shapes, refchecked vs torch.matmul."""
+"""Micro-benchmark: gemm_bt (128x128 m97 structure) vs the experimental
+gemm_bt_8p3 (256x256) on square + ResNet conv shapes, refchecked vs
+torch.matmul."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,7 +27,6 @@ def run(M, N, K, check=True):
     if check:
         ref = (A[:512].float() @ B.float().t())
         for name, fn in [("bt", lambda: _C.gemm_bt(A, B, False)),
-                         ("8p", lambda: _C.gemm_bt_8p(A, B)),
                          ("8p3", lambda: _C.gemm_bt_8p3(A, B))]:
             out = fn()[:512].float()
             err = (out - ref).abs().max().item()
@@ -37,10 +37,8 @@ def run(M, N, K, check=True):
                 return
     flops = 2.0 * M * N * K
     t_bt = time_fn(lambda: _C.gemm_bt(A, B, False))
-    t_8p = time_fn(lambda: _C.gemm_bt_8p(A, B))
     t_83 = time_fn(lambda: _C.gemm_bt_8p3(A, B))
     print(f"M={M} N={N} K={K}: bt {t_bt*1e6:8.1f} us ({flops/t_bt/1e12:7.1f} TF)"
-          f" | 8p {t_8p*1e6:8.1f} us ({flops/t_8p/1e12:7.1f} TF)"
           f" | 8p3 {t_83*1e6:8.1f} us ({flops/t_83/1e12:7.1f} TF)", flush=True)
 
 
