@@ -9,8 +9,15 @@ unchanged.
 Every conv is an ``AmdConv2d``: the 17 depthwise 3x3 layers run on the
 stencil kernels of ``ops/csrc/dwconv.hip``; the pointwise layers and the stem
 take whatever path ``AmdConv2d`` has for their shape (docs/KERNELS.md lists
-them).  Every BN is a ``FusedBatchNorm2d`` called with ``relu=False`` and
-followed by ``F.relu6``: ReLU6 is not fused into the BN kernels.
+them).  Every BN is a ``FusedBatchNorm2d`` that runs through
+``ops.fused.batch_norm``: the 35 BN -> ReLU6 pairs with ``relu6=True``, one
+apply pass with the clamp in its epilogue, and the 17 linear-bottleneck BNs
+without an activation, the 10 of them that close an identity shortcut with
+the shortcut as the BN's ``addend``, so that ``x + out`` is no pass of its
+own in either direction.  The widths that are no power of two (42 of the 52
+BNs) run on the any-C kernels of ``ops/csrc/batchnorm_anyc.h``.  A width
+those kernels do not take (fp32 without autocast: C = 1280 is 320 packs)
+keeps BN followed by ``F.relu6``.
 """
 
 from __future__ import annotations
@@ -73,7 +80,12 @@ class ConvBNReLU6(nn.Sequential):
         )
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return F.relu6(OF.batch_norm(self[0](x), self[1], relu=False))
+        y = self[0](x)
+        if OF.bn_relu6_fusable(y):
+            return OF.batch_norm(y, self[1], relu6=True)
+        # no ReLU6 kernel for this width and dtype (fp32 C = 1280): the
+        # two ops, as before the fusion
+        return F.relu6(OF.batch_norm(y, self[1], relu=False))
 
 
 class InvertedResidual(nn.Module):
@@ -100,9 +112,10 @@ class InvertedResidual(nn.Module):
         out = x
         for i in range(self._n_act):   # expand (if any) and depthwise
             out = self.conv[i](out)
-        out = OF.batch_norm(self.conv[self._n_act](out),
-                            self.conv[self._n_act + 1], relu=False)
-        return x + out if self.use_res_connect else out
+        # the identity shortcut rides in the BN apply as its addend
+        return OF.batch_norm(self.conv[self._n_act](out),
+                             self.conv[self._n_act + 1], relu=False,
+                             addend=x if self.use_res_connect else None)
 
 
 class MobileNetV2(nn.Module):

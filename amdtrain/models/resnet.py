@@ -54,12 +54,13 @@ def conv1x1(in_planes: int, out_planes: int, stride: int = 1) -> nn.Conv2d:
 
 
 class FusedBatchNorm2d(nn.BatchNorm2d):
-    """BatchNorm2d whose forward can fuse the trailing ReLU.
+    """BatchNorm2d whose forward can fuse the trailing ReLU or ReLU6.
 
     Parameter/buffer names are identical to ``nn.BatchNorm2d`` so state_dicts
     interoperate.  ``forward_relu`` is the fused entrypoint used inside the
-    residual blocks; it routes through ``amdtrain.ops.fused.batch_norm`` which
-    selects the hand-written NHWC HIP kernel on GPU.
+    residual blocks (``forward_relu6``: its ReLU6 twin); it routes through
+    ``amdtrain.ops.fused.batch_norm`` which selects the hand-written NHWC HIP
+    kernel on GPU.
     """
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:  # type: ignore[override]
@@ -67,6 +68,9 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
 
     def forward_relu(self, x: torch.Tensor) -> torch.Tensor:
         return OF.batch_norm(x, self, relu=True)
+
+    def forward_relu6(self, x: torch.Tensor) -> torch.Tensor:
+        return OF.batch_norm(x, self, relu6=True)
 
 
 def _shortcut_tail(out: torch.Tensor, bn: FusedBatchNorm2d,

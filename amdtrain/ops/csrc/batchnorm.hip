@@ -16,10 +16,16 @@
 // phase-reduction per block into per-block partials that a second stage
 // sums in a fixed order (no global atomics).
 // All ResNet channel counts (64..2048) hit this register path.
+//
+// These kernels take power-of-two C only.  Any other C with whole 16-byte
+// packs and at most 256 of them per row, and every ReLU6, runs on the
+// kernels of batchnorm_anyc.h, behind the same entries and the same
+// collapse / finalize stages.
 #include <cstdlib>
 #include <cstring>
 
 #include "common.h"
+#include "batchnorm_anyc.h"
 
 namespace {
 
@@ -806,6 +812,53 @@ static void dispatch_vec(const at::Tensor& x, F fn) {
       });
 }
 
+static bool bn_pow2(long C) { return (C & (C - 1)) == 0; }
+
+// the forward / backward activation selector of the entries' two flags
+static int bn_act(bool relu, bool relu6) {
+  TORCH_CHECK(!(relu && relu6), "batch_norm: relu and relu6 are exclusive");
+  return relu6 ? BN_ACT_RELU6 : relu ? BN_ACT_RELU : BN_ACT_NONE;
+}
+
+// which family serves (C, act): the power-of-two kernels keep every shape
+// they served before ReLU6 existed
+static bool bn_use_anyc(long C, int act) {
+  return !bn_pow2(C) || act == BN_ACT_RELU6;
+}
+
+// the any-C contract: whole 16-byte packs, one channel group per thread
+static void bn_check_anyc_channels(const at::Tensor& x) {
+  const long C = x.size(1);
+  const long vec = 16 / (long)x.element_size();
+  TORCH_CHECK(C > 0 && C % vec == 0 && C / vec <= AMD_TPB,
+              "batch_norm: C must be a multiple of ", vec, " and at most ",
+              vec * AMD_TPB, " for this dtype, got ", C);
+}
+
+// forward entries: refuse what the any-C family does not build before any
+// kernel runs (the statistics stage updates the running stats in place)
+static void bn_check_fwd_form(const at::Tensor& x, int act,
+                              const std::optional<at::Tensor>& addend) {
+  const long C = x.size(1);
+  if (!bn_use_anyc(C, act)) return;
+  bn_check_anyc_channels(x);
+  TORCH_CHECK(!(addend && act != BN_ACT_NONE), "batch_norm: an addend under ",
+              act == BN_ACT_RELU6 ? "ReLU6" : "ReLU",
+              " is not built for this channel count: C = ", C);
+}
+
+template <typename F>
+static void dispatch_vec_anyc(const at::Tensor& x, F fn) {
+  bn_check_anyc_channels(x);
+  AT_DISPATCH_FLOATING_TYPES_AND2(
+      at::ScalarType::BFloat16, at::ScalarType::Half, x.scalar_type(),
+      "bn_anyc", [&] {
+        using devT = typename DevT<scalar_t>::type;
+        constexpr int VEC = 16 / sizeof(devT);
+        fn((devT*)nullptr, std::integral_constant<int, VEC>{});
+      });
+}
+
 // AMDTRAIN_BN_REGCOEF=0 keeps the single-BN applies on the LDS coefficient
 // path (A/B switch; read per call so one process can compare both)
 static bool bn_regcoef_enabled() {
@@ -818,10 +871,40 @@ static void bn_apply_launch(const at::Tensor& x,
                             const std::optional<at::Tensor>& addend,
                             at::Tensor& y, const at::Tensor& mask,
                             const at::Tensor& scale, const at::Tensor& shift,
-                            bool relu) {
+                            int act) {
   const long C = x.size(1);
   const long R = x.numel() / C;
   auto stream = at::cuda::getCurrentCUDAStream();
+  if (bn_use_anyc(C, act)) {
+    if (addend) {
+      check_nhwc(*addend);
+      TORCH_CHECK(addend->sizes() == x.sizes() &&
+                      addend->scalar_type() == x.scalar_type(),
+                  "batch_norm: addend must match x in shape and dtype");
+    }
+    // (bn_check_fwd_form has refused an addend under an activation)
+    dispatch_vec_anyc(x, [&](auto* tp, auto vec) {
+      using devT = std::remove_pointer_t<decltype(tp)>;
+      constexpr int VEC = decltype(vec)::value;
+      const long total_vec = R * C / VEC;
+      const int nt = bn_anyc_block((int)(C / VEC));
+      const int agrid = amd_grid(total_vec, nt);
+      const devT* zp =
+          addend ? (const devT*)addend->const_data_ptr() : nullptr;
+#define APPLY_ANYC(ACT_, ADD_)                                              \
+  bn_anyc_apply_kernel<devT, VEC, ACT_, ADD_><<<agrid, nt, 0, stream>>>(    \
+      (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),             \
+      scale.data_ptr<float>(), shift.data_ptr<float>(), total_vec, (int)C)
+      if (addend) APPLY_ANYC(BN_ACT_NONE, true);
+      else if (act == BN_ACT_RELU6) APPLY_ANYC(BN_ACT_RELU6, false);
+      else if (act == BN_ACT_RELU) APPLY_ANYC(BN_ACT_RELU, false);
+      else APPLY_ANYC(BN_ACT_NONE, false);
+#undef APPLY_ANYC
+      CHECK_CUDA_OK();
+    });
+    return;
+  }
+  const bool relu = act == BN_ACT_RELU;
   dispatch_vec(x, [&](auto* tp, auto vec) {
     using devT = std::remove_pointer_t<decltype(tp)>;
     constexpr int VEC = decltype(vec)::value;
@@ -903,7 +986,17 @@ static BNTrainStats bn_train_stats(const at::Tensor& x,
   } else {
     const int rgrid = bn_reduce_grid(R, C);
     sums = at::empty({rgrid, 2 * C}, opts);
-    dispatch_vec(x, [&](auto* tp, auto vec) {
+    if (!bn_pow2(C))
+      dispatch_vec_anyc(x, [&](auto* tp, auto vec) {
+        using devT = std::remove_pointer_t<decltype(tp)>;
+        constexpr int VEC = decltype(vec)::value;
+        bn_anyc_reduce_kernel<devT, VEC, false, BN_ACT_NONE>
+            <<<rgrid, bn_anyc_block((int)(C / VEC)), 0, stream>>>(
+                (const devT*)x.const_data_ptr(), nullptr, nullptr, nullptr,
+                nullptr, nullptr, sums.data_ptr<float>(), R, (int)C);
+        CHECK_CUDA_OK();
+      });
+    else dispatch_vec(x, [&](auto* tp, auto vec) {
       using devT = std::remove_pointer_t<decltype(tp)>;
       constexpr int VEC = decltype(vec)::value;
       bn_reduce_kernel<devT, VEC, false, 0, false, false>
@@ -1016,21 +1109,24 @@ std::vector<at::Tensor> batch_norm_train_stats(
 std::vector<at::Tensor> batch_norm_fwd_train(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
     at::Tensor running_var, double momentum, double eps, bool relu,
-    std::optional<at::Tensor> addend) {
+    std::optional<at::Tensor> addend, bool relu6) {
   check_nhwc(x);
+  const int act = bn_act(relu, relu6);
+  bn_check_fwd_form(x, act, addend);
   const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const long R = N * H * W;
   auto y = at::empty_like(x);
   // block-tail BNs (relu+addend) also emit a 1-bit relu mask (1/16 the
   // bytes of y) so the bwd reduce skips the y read entirely
   at::Tensor mask;
-  if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
+  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
+  if (relu && addend && !bn_use_anyc(C, act))
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
   auto st = bn_train_stats(x, std::nullopt, weight, bias, running_mean,
                            running_var, momentum, eps);
   auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
        &shift = st.shift;
-  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
+  bn_apply_launch(x, addend, y, mask, scale, shift, act);
   if (!mask.defined()) mask = at::empty({0}, x.options().dtype(at::kByte));
   return {y, mean, invstd, scale, shift, mask};
 }
@@ -1040,19 +1136,22 @@ std::vector<at::Tensor> batch_norm_fwd_train(
 std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
     at::Tensor x, at::Tensor parts, at::Tensor weight, at::Tensor bias,
     at::Tensor running_mean, at::Tensor running_var, double momentum,
-    double eps, bool relu, std::optional<at::Tensor> addend) {
+    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6) {
   check_nhwc(x);
+  const int act = bn_act(relu, relu6);
+  bn_check_fwd_form(x, act, addend);
   const long C = x.size(1);
   const long R = x.numel() / C;
   auto y = at::empty_like(x);
   at::Tensor mask;
-  if (relu && addend)  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
+  // one byte per VEC-pack; VEC is 4 for fp32 (16B/4B)
+  if (relu && addend && !bn_use_anyc(C, act))
     mask = at::empty({R * C / 4}, x.options().dtype(at::kByte));
   auto st = bn_train_stats(x, parts, weight, bias, running_mean, running_var,
                            momentum, eps);
   auto &mean = st.mean, &invstd = st.invstd, &scale = st.scale,
        &shift = st.shift;
-  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
+  bn_apply_launch(x, addend, y, mask, scale, shift, act);
   if (!mask.defined()) mask = at::empty({0}, x.options().dtype(at::kByte));
   return {y, mean, invstd, scale, shift, mask};
 }
@@ -1160,8 +1259,10 @@ std::vector<at::Tensor> batch_norm_dual_bwd(
 at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
-                               std::optional<at::Tensor> addend) {
+                               std::optional<at::Tensor> addend, bool relu6) {
   check_nhwc(x);
+  const int act = bn_act(relu, relu6);
+  bn_check_fwd_form(x, act, addend);
   const long C = x.size(1);
   const long R = x.numel() / C;
   auto opts = x.options().dtype(at::kFloat);
@@ -1176,7 +1277,7 @@ at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
       running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
       scale.data_ptr<float>(), shift.data_ptr<float>(), (int)C, (float)eps);
   CHECK_CUDA_OK();
-  bn_apply_launch(x, addend, y, mask, scale, shift, relu);
+  bn_apply_launch(x, addend, y, mask, scale, shift, act);
   return y;
 }
 
@@ -1189,7 +1290,8 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
                                        std::optional<at::Tensor> relu_mask,
-                                       bool grad_out2_compact) {
+                                       bool grad_out2_compact, bool relu6) {
+  // relu6, or a C that is not a power of two: the any-C kernels (below).
   // grad_out2_compact: grad_out2 is the [N*Hs*Ws, C] dgrad of a stride-2
   // 1x1 conv (Hs = ceil(H/2), Ws = ceil(W/2)); the reduce reads it at the
   // even positions and adds 0 elsewhere, which is the tensor
@@ -1206,6 +1308,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   //                            disappears entirely (2 passes saved)
   check_nhwc(x);
   check_nhwc(grad_out);
+  const int act = bn_act(relu, relu6);
   const long C = x.size(1);
   const long R = x.numel() / C;
   auto opts = x.options().dtype(at::kFloat);
@@ -1213,6 +1316,55 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   auto sums = at::empty({rgrid, 2 * C}, opts);
   BNBwdCoeffs k;
   auto gx = at::empty_like(x);
+  if (bn_use_anyc(C, act)) {
+    TORCH_CHECK(grad_out.sizes() == x.sizes() &&
+                    grad_out.scalar_type() == x.scalar_type(),
+                "batch_norm_bwd: grad_out must match x in shape and dtype");
+    // Two passes, neither reads y: reduce(x, go) -> apply(x, go -> gx),
+    // each masking go by the activation recomputed from scale / shift.
+    // With an addend (no activation) its gradient is grad_out itself.
+    TORCH_CHECK(!grad_out2.has_value(),
+                "batch_norm_bwd: grad_out2 (the block-tail mailbox) is "
+                "power-of-two C and ReLU only: C = ", C);
+    TORCH_CHECK(!(need_ghat && act != BN_ACT_NONE),
+                "batch_norm_bwd: an addend under an activation is not built "
+                "for this channel count: C = ", C);
+    TORCH_CHECK(act == BN_ACT_NONE || (scale && shift),
+                "batch_norm_bwd: the activation mask needs the forward's "
+                "scale and shift");
+    dispatch_vec_anyc(x, [&](auto* tp, auto vec) {
+      using devT = std::remove_pointer_t<decltype(tp)>;
+      constexpr int VEC = decltype(vec)::value;
+      auto stream = at::cuda::getCurrentCUDAStream();
+      const float* scp = act != BN_ACT_NONE ? scale->data_ptr<float>()
+                                            : nullptr;
+      const float* shp = act != BN_ACT_NONE ? shift->data_ptr<float>()
+                                            : nullptr;
+      const devT* xp = (const devT*)x.const_data_ptr();
+      const devT* gop = (const devT*)grad_out.const_data_ptr();
+      const int nt = bn_anyc_block((int)(C / VEC));
+      const long total_vec = R * C / VEC;
+      const int agrid = amd_grid(total_vec, nt);
+#define BWD_ANYC(ACT_)                                                      \
+  do {                                                                      \
+    bn_anyc_reduce_kernel<devT, VEC, true, ACT_><<<rgrid, nt, 0, stream>>>( \
+        xp, gop, mean.data_ptr<float>(), invstd.data_ptr<float>(), scp,     \
+        shp, sums.data_ptr<float>(), R, (int)C);                            \
+    CHECK_CUDA_OK();                                                        \
+    k = bn_bwd_coeffs(sums, weight, mean, invstd, R, C);                    \
+    bn_anyc_bwd_apply_kernel<devT, VEC, ACT_><<<agrid, nt, 0, stream>>>(    \
+        xp, gop, (devT*)gx.data_ptr(), k.A.data_ptr<float>(),               \
+        k.Bc.data_ptr<float>(), k.Dc.data_ptr<float>(), scp, shp,           \
+        total_vec, (int)C);                                                 \
+    CHECK_CUDA_OK();                                                        \
+  } while (0)
+      if (act == BN_ACT_RELU6) BWD_ANYC(BN_ACT_RELU6);
+      else if (act == BN_ACT_RELU) BWD_ANYC(BN_ACT_RELU);
+      else BWD_ANYC(BN_ACT_NONE);
+#undef BWD_ANYC
+    });
+    return {gx, k.gw, k.gb, grad_out};
+  }
   const bool affine_mask = relu && !need_ghat && scale && shift;
   // grad_out2 (rerouted residual gradient) forces the ghat-writing path so
   // the fp32 sum is materialized once

@@ -27,19 +27,20 @@ void multi_tensor_scale_check(std::vector<at::Tensor> tensors, double scale,
 void multi_tensor_cast(std::vector<at::Tensor> src,
                        std::vector<at::Tensor> dst);
 
-// batchnorm.hip
+// batchnorm.hip (relu6, trailing and defaulted: ReLU6 in place of relu;
+// any channel count with whole 16-byte packs, at most 256 per row)
 std::vector<at::Tensor> batch_norm_fwd_train(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
     at::Tensor running_var, double momentum, double eps, bool relu,
-    std::optional<at::Tensor> addend);
+    std::optional<at::Tensor> addend, bool relu6);
 std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
     at::Tensor x, at::Tensor parts, at::Tensor weight, at::Tensor bias,
     at::Tensor running_mean, at::Tensor running_var, double momentum,
-    double eps, bool relu, std::optional<at::Tensor> addend);
+    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6);
 at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
-                               std::optional<at::Tensor> addend);
+                               std::optional<at::Tensor> addend, bool relu6);
 std::vector<at::Tensor> batch_norm_train_stats(
     at::Tensor x, std::optional<at::Tensor> parts, at::Tensor weight,
     at::Tensor bias, at::Tensor running_mean, at::Tensor running_var,
@@ -65,7 +66,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
                                        std::optional<at::Tensor> relu_mask,
-                                       bool grad_out2_compact);
+                                       bool grad_out2_compact, bool relu6);
 std::vector<at::Tensor> batch_norm_bwd_pool(
     at::Tensor x, at::Tensor grad_pool, std::optional<at::Tensor> grad_pool2,
     at::Tensor idx, at::Tensor weight, at::Tensor mean, at::Tensor invstd,
@@ -149,15 +150,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
         py::arg("eps"), py::arg("relu"),
-        py::arg("addend") = std::nullopt);
+        py::arg("addend") = std::nullopt, py::arg("relu6") = false);
   m.def("batch_norm_fwd_train_from_parts", &batch_norm_fwd_train_from_parts,
         py::arg("x"), py::arg("parts"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
-        py::arg("eps"), py::arg("relu"), py::arg("addend") = std::nullopt);
+        py::arg("eps"), py::arg("relu"), py::arg("addend") = std::nullopt,
+        py::arg("relu6") = false);
   m.def("batch_norm_fwd_eval", &batch_norm_fwd_eval,
         py::arg("x"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("eps"),
-        py::arg("relu"), py::arg("addend") = std::nullopt);
+        py::arg("relu"), py::arg("addend") = std::nullopt,
+        py::arg("relu6") = false);
   m.def("batch_norm_train_stats", &batch_norm_train_stats);
   m.def("batch_norm_dual_fwd_train", &batch_norm_dual_fwd_train);
   m.def("batch_norm_dual_bwd", &batch_norm_dual_bwd);
@@ -167,7 +170,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = std::nullopt, py::arg("shift") = std::nullopt,
         py::arg("grad_out2") = std::nullopt,
         py::arg("relu_mask") = std::nullopt,
-        py::arg("grad_out2_compact") = false);
+        py::arg("grad_out2_compact") = false, py::arg("relu6") = false);
   m.def("batch_norm_bwd_pool", &batch_norm_bwd_pool, py::arg("x"),
         py::arg("grad_pool"), py::arg("grad_pool2"), py::arg("idx"),
         py::arg("weight"), py::arg("mean"), py::arg("invstd"),

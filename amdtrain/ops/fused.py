@@ -1,4 +1,4 @@
-"""Model-facing fused NHWC ops: BatchNorm(+add)(+ReLU), pooling.
+"""Model-facing fused NHWC ops: BatchNorm(+add)(+ReLU/ReLU6), pooling.
 
 The reference runs BN and ReLU as separate cuDNN/elementwise kernels after
 every conv (53 BN layers in ResNet-50) — on MI355X that is pure
@@ -21,34 +21,38 @@ import torch.nn.functional as F
 from ._ext import require_ext, use_ext_for
 from .conv import GradCell, _dsgrad_compact_enabled
 
-__all__ = ["batch_norm", "bn_add_relu", "bn_add_relu_downsample",
+__all__ = ["batch_norm", "bn_relu6_fusable", "bn_add_relu", "bn_add_relu_downsample",
            "bn_relu_max_pool", "max_pool_3x3_s2", "global_avg_pool"]
 
 
 class _BNFunction(torch.autograd.Function):
-    """Fused BN(+add)(+ReLU) training-mode forward/backward on NHWC GPU
-    tensors.  When the producing conv attached per-block statistics
+    """Fused BN(+add)(+ReLU/ReLU6) training-mode forward/backward on NHWC
+    GPU tensors.  When the producing conv attached per-block statistics
     partials (conv epilogue fusion), the reduce pass over x is skipped."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
-                momentum, eps, relu, addend, parts, res_cell=None):
+                momentum, eps, relu, addend, parts, res_cell=None,
+                relu6=False):
         e = require_ext()
         if parts is not None:
             y, mean, invstd, scale, shift, mask = \
                 e.batch_norm_fwd_train_from_parts(
                     x, parts, weight, bias, running_mean, running_var,
-                    float(momentum), float(eps), bool(relu), addend)
+                    float(momentum), float(eps), bool(relu), addend,
+                    bool(relu6))
         else:
             y, mean, invstd, scale, shift, mask = e.batch_norm_fwd_train(
                 x, weight, bias, running_mean, running_var,
-                float(momentum), float(eps), bool(relu), addend)
+                float(momentum), float(eps), bool(relu), addend,
+                bool(relu6))
         # scale/shift ([C] fp32) let the bwd recompute the relu mask as
         # scale*x+shift>0 for addend-free BNs; block-tail BNs save the
         # fwd-computed 1-bit relu mask instead (bwd skips the y read)
         ctx.save_for_backward(x, y, weight, mean, invstd, scale, shift,
                               mask)
         ctx.relu = bool(relu)
+        ctx.relu6 = bool(relu6)
         ctx.has_addend = addend is not None
         # block-tail BN grad mailbox (see batch_norm below): our backward
         # folds a rerouted shortcut gradient into the reduce as a second
@@ -75,14 +79,15 @@ class _BNFunction(torch.autograd.Function):
         grad_x, grad_w, grad_b, ghat = e.batch_norm_bwd(
             x, grad_out.contiguous(memory_format=torch.channels_last),
             y, weight, mean, invstd, ctx.relu, ctx.has_addend,
-            scale, shift, go2, mask, compact)
+            scale, shift, go2, mask, compact, ctx.relu6)
         grad_addend = ghat if ctx.has_addend else None
         return (grad_x, grad_w, grad_b, None, None, None, None, None,
-                grad_addend, None, None)
+                grad_addend, None, None, None)
 
 
 def _bn_torch(x: torch.Tensor, bn, relu: bool,
-              addend: Optional[torch.Tensor]) -> torch.Tensor:
+              addend: Optional[torch.Tensor],
+              relu6: bool = False) -> torch.Tensor:
     """Plain-torch reference path (CPU, or GPU with ext disabled)."""
     # match nn.BatchNorm2d bookkeeping (num_batches_tracked handled by caller)
     y = F.batch_norm(
@@ -93,17 +98,55 @@ def _bn_torch(x: torch.Tensor, bn, relu: bool,
         y = y + addend
     if relu:
         y = F.relu(y, inplace=True)
+    if relu6:
+        y = F.relu6(y)
     return y
 
 
+def _anyc_ok(x: torch.Tensor) -> bool:
+    """The any-C kernels' channel contract: whole 16-byte packs, at most 256
+    of them per row (one channel group per thread of a block)."""
+    C = x.size(1)
+    vec = 16 // x.element_size()
+    return C > 0 and C % vec == 0 and C // vec <= 256
+
+
+def bn_relu6_fusable(x: torch.Tensor) -> bool:
+    """Whether ``batch_norm(x, bn, relu6=True)`` has a path for ``x``: always
+    off the extension (plain torch ops), on it only inside the any-C
+    kernels' channel contract."""
+    return not use_ext_for(x) or _anyc_ok(x)
+
+
 def batch_norm(x: torch.Tensor, bn, relu: bool = False,
-               addend: Optional[torch.Tensor] = None) -> torch.Tensor:
+               addend: Optional[torch.Tensor] = None,
+               relu6: bool = False) -> torch.Tensor:
     """BatchNorm2d through module ``bn``'s parameters/buffers, optionally fused
-    with a residual add and/or ReLU."""
+    with a residual add and/or ReLU, or with ReLU6 (no addend).
+
+    On the GPU a power-of-two C without ReLU6 runs on the kernels it always
+    did.  Any other C inside ``_anyc_ok``, and every ReLU6, runs on the any-C
+    kernels, except ReLU with an addend (the block tail, power-of-two
+    only).  Without ReLU6, what is left takes the library BN as it always
+    did.  ReLU6 outside ``_anyc_ok`` (C % VEC != 0, or more than 256 packs
+    per row such as fp32 C = 1280) has no kernel and is an error here, not a
+    library composition: see ``bn_relu6_fusable``."""
+    if relu and relu6:
+        raise ValueError("batch_norm: relu and relu6 are mutually exclusive")
+    if relu6 and addend is not None:
+        raise ValueError("batch_norm: relu6 with an addend is not supported")
+    C = x.size(1)
+    pow2 = (C & (C - 1)) == 0
+    on_ext = use_ext_for(x)
+    if on_ext and relu6 and not _anyc_ok(x):
+        raise NotImplementedError(
+            f"batch_norm: no ReLU6 kernel for C = {C} in {x.dtype} (needs "
+            f"whole 16-byte packs, at most 256 per row)")
+    if on_ext and not pow2:
+        on_ext = _anyc_ok(x) and not (relu and addend is not None)
     if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    C = x.size(1)
-    if use_ext_for(x) and (C & (C - 1)) == 0:  # kernels take pow2 C only
+    if on_ext:
         parts = getattr(x, "_amdtrain_bn_stats", None) if bn.training else None
         xc = x.contiguous(memory_format=torch.channels_last)
         ac = None if addend is None else addend.contiguous(memory_format=torch.channels_last)
@@ -118,14 +161,14 @@ def batch_norm(x: torch.Tensor, bn, relu: bool = False,
                                    and _vec_ok(xc, 256))
             out = _BNFunction.apply(xc, bn.weight, bn.bias, bn.running_mean,
                                     bn.running_var, bn.momentum, bn.eps,
-                                    relu, ac, parts, cell)
+                                    relu, ac, parts, cell, relu6)
             if cell is not None:
                 out._amdtrain_next_cell = cell
             return out
         return require_ext().batch_norm_fwd_eval(
             xc, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-            float(bn.eps), bool(relu), ac)
-    return _bn_torch(x, bn, relu, addend)
+            float(bn.eps), bool(relu), ac, bool(relu6))
+    return _bn_torch(x, bn, relu, addend, relu6)
 
 
 def bn_add_relu(x: torch.Tensor, bn, addend: torch.Tensor) -> torch.Tensor:
