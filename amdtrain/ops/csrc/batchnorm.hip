@@ -389,6 +389,63 @@ __global__ void bn_collapse_partials_kernel(const float* __restrict__ in,
   out[(long)slot * twoC + c] = acc;
 }
 
+// The same fold, streaming: one thread owns VEC adjacent columns of one slot
+// (VEC = 4: 16 B loads; VEC = 1 serves twoC % 4 != 0 or a misaligned base),
+// work items are laid slot-major over the whole grid so every thread of a
+// block has one (twoC = 128: a 256-thread block covers 8 slots), and the
+// row loads of a batch of BN_COLLAPSE_U rows are all issued before the
+// first add.  The adds then run in the kernel above's order — acc = 0.f,
+// rows slot, slot + slots, ... one by one — so every output bit is the same.
+constexpr int BN_COLLAPSE_U = 8;
+
+template <int VEC>
+__global__ void bn_collapse_partials_stream_kernel(
+    const float* __restrict__ in, float* __restrict__ out, int nparts,
+    int twoC, int slots) {
+  using Vec = Pack<float, VEC>;
+  const int cols = twoC / VEC;  // column groups per row
+  const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= (long)slots * cols) return;
+  const int slot = (int)(item / cols);
+  const int c = (int)(item % cols) * VEC;
+  const float* src = in + (long)slot * twoC + c;
+  const long step = (long)slots * twoC;
+  float acc[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+  int p = slot;
+  // full batches: U independent loads in flight, then U ordered adds
+  for (; p + (BN_COLLAPSE_U - 1) * slots < nparts;
+       p += BN_COLLAPSE_U * slots, src += BN_COLLAPSE_U * step) {
+    Vec v[BN_COLLAPSE_U];
+#pragma unroll
+    for (int u = 0; u < BN_COLLAPSE_U; ++u)
+      v[u] = *(const Vec*)(src + u * step);
+#pragma unroll
+    for (int u = 0; u < BN_COLLAPSE_U; ++u)
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) acc[k] += v[u].v[k];
+  }
+  if (p < nparts) {
+    // last, partial batch, still branch-free: a row past the end reads row
+    // 0 instead and adds +0.f, which changes no bit (acc starts at +0.f and
+    // a sum of round-to-nearest adds from +0.f is never -0.f)
+    Vec v[BN_COLLAPSE_U];
+#pragma unroll
+    for (int u = 0; u < BN_COLLAPSE_U; ++u)
+      v[u] = *(const Vec*)(p + u * slots < nparts ? src + u * step : in + c);
+#pragma unroll
+    for (int u = 0; u < BN_COLLAPSE_U; ++u)
+#pragma unroll
+      for (int k = 0; k < VEC; ++k)
+        acc[k] += p + u * slots < nparts ? v[u].v[k] : 0.f;
+  }
+  Vec o;
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) o.v[k] = acc[k];
+  *(Vec*)(out + (long)slot * twoC + c) = o;
+}
+
 // ---- finalize (train): stats + running update + scale/shift ---------------
 // 4 slot-threads per channel (the single-thread row loop over up to 128
 // collapse slots was ~20 us latency-bound x 106 calls/step)
@@ -947,16 +1004,38 @@ static int bn_reduce_grid(long R, int C) {
 }
 
 // collapse [nparts][2C] per-block partials to the few slots the finalize
-// kernels loop over
+// kernels loop over.  impl: 1 the streaming kernel, 0 the one-column-per-
+// thread kernel it replaced (AMDTRAIN_BN_COLLAPSE=0), negative = the
+// environment, else 1; both give the same bits.
 static at::Tensor bn_collapse(const at::Tensor& parts, long C,
-                              hipStream_t stream) {
+                              hipStream_t stream, long impl = -1) {
+  static const int env = []() {
+    const char* e = std::getenv("AMDTRAIN_BN_COLLAPSE");
+    return e ? (e[0] == '0' ? 0 : 1) : -1;
+  }();
+  if (impl < 0) impl = env >= 0 ? env : 1;
   const int nparts = (int)parts.size(0);
   const int slots = bn_collapse_slots(nparts);
+  const int twoC = (int)(2 * C);
   auto sums2 = at::empty({slots, 2 * C}, parts.options());
-  int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
-  bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
-      parts.data_ptr<float>(), sums2.data_ptr<float>(), nparts, (int)(2 * C),
-      slots);
+  const float* in = parts.data_ptr<float>();
+  float* out = sums2.data_ptr<float>();
+  if (impl == 0) {
+    int cgrid = slots * (int)((2 * C + AMD_TPB - 1) / AMD_TPB);
+    bn_collapse_partials_kernel<<<cgrid, AMD_TPB, 0, stream>>>(
+        in, out, nparts, twoC, slots);
+  } else {
+    const bool vec = twoC % 4 == 0 && (uintptr_t)in % 16 == 0 &&
+                     (uintptr_t)out % 16 == 0;
+    const long items = (long)slots * (vec ? twoC / 4 : twoC);
+    const int cgrid = (int)((items + AMD_TPB - 1) / AMD_TPB);
+    if (vec)
+      bn_collapse_partials_stream_kernel<4><<<cgrid, AMD_TPB, 0, stream>>>(
+          in, out, nparts, twoC, slots);
+    else
+      bn_collapse_partials_stream_kernel<1><<<cgrid, AMD_TPB, 0, stream>>>(
+          in, out, nparts, twoC, slots);
+  }
   CHECK_CUDA_OK();
   return sums2;
 }
@@ -1093,6 +1172,17 @@ static void check_dual(const at::Tensor& x3, const at::Tensor& x_d) {
 }
 
 }  // namespace
+
+// the fold on its own (tests, tools): parts [nparts][2C] fp32 -> [slots][2C]
+at::Tensor bn_collapse_partials(at::Tensor parts, long impl) {
+  TORCH_CHECK(parts.is_cuda() && parts.dim() == 2 &&
+              parts.scalar_type() == at::kFloat && parts.size(0) >= 1 &&
+              parts.size(1) % 2 == 0, "parts must be fp32 [nparts][2C]");
+  TORCH_CHECK(parts.stride(1) == 1 && parts.stride(0) == parts.size(1),
+              "parts must be dense (a storage offset is fine)");
+  return bn_collapse(parts, parts.size(1) / 2,
+                     at::cuda::getCurrentCUDAStream(), impl);
+}
 
 // statistics stage alone (mean, invstd, scale, shift + running update) for
 // consumers that apply scale/shift inside their own kernel (stem max pool)

@@ -41,6 +41,7 @@ at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
                                std::optional<at::Tensor> addend, bool relu6);
+at::Tensor bn_collapse_partials(at::Tensor parts, long impl);
 std::vector<at::Tensor> batch_norm_train_stats(
     at::Tensor x, std::optional<at::Tensor> parts, at::Tensor weight,
     at::Tensor bias, at::Tensor running_mean, at::Tensor running_var,
@@ -162,6 +163,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu"), py::arg("addend") = std::nullopt,
         py::arg("relu6") = false);
   m.def("batch_norm_train_stats", &batch_norm_train_stats);
+  // impl: 1 streaming fold, 0 the kernel it replaced, -1 =
+  // AMDTRAIN_BN_COLLAPSE or 1
+  m.def("bn_collapse_partials", &bn_collapse_partials, py::arg("parts"),
+        py::arg("impl") = -1);
   m.def("batch_norm_dual_fwd_train", &batch_norm_dual_fwd_train);
   m.def("batch_norm_dual_bwd", &batch_norm_dual_bwd);
   m.def("batch_norm_bwd", &batch_norm_bwd, py::arg("x"), py::arg("grad_out"),
