@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import fused as OF
-from ..ops.conv import AmdConv2d
+from ..ops.conv import AmdConv2d, _pwconv_enabled, pw_thin_ok
 from ..ops.linear import AmdLinear
 from .resnet import FusedBatchNorm2d
 
@@ -46,17 +46,26 @@ _SETTINGS = [
 
 
 class LibraryConv2d(AmdConv2d):
-    """An ``AmdConv2d`` pinned to the library (``nn.Conv2d``) path."""
+    """An ``AmdConv2d`` that keeps off the MFMA GEMM: it runs on the thin
+    pointwise kernel when that is enabled and takes the layer, and on the
+    library (``nn.Conv2d``) path otherwise."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if (_pwconv_enabled() and self.kernel_size == (1, 1)
+                and self.stride == (1, 1)
+                and pw_thin_ok(self.in_channels, self.out_channels)):
+            return AmdConv2d.forward(self, x)
         return nn.Conv2d.forward(self, x)
 
 
 def _pointwise(inp: int, oup: int) -> AmdConv2d:
-    """1x1 conv.  ``AmdConv2d`` sends in % 32 == 0, out % 16 == 0 to the
-    MFMA GEMM, whose input gradient then needs out % 32 == 0 as its K and
-    raises otherwise; the one such layer here (32 -> 16, features.1) stays
-    on the library path until the GEMM takes that K (TODO.md).
+    """1x1 conv.  ``AmdConv2d`` sends in % 32 == 0, out % 32 == 0 to the
+    MFMA GEMM and the other widths of this model (``pw_thin_ok``) to the thin
+    pointwise kernel of ``ops/csrc/pwconv.hip``.  With that kernel switched
+    off (AMDTRAIN_PWCONV=0) in % 32 == 0, out % 16 == 0 goes to the GEMM,
+    whose input gradient then needs out % 32 == 0 as its K and raises
+    otherwise; the one such layer here (32 -> 16, features.1) is a
+    ``LibraryConv2d``, which takes the library path in that case.
 
     The first two terms of the condition repeat ``ch_ok`` of
     ``AmdConv2d.forward`` (ops/conv.py); if that guard changes, change this

@@ -4,7 +4,9 @@ A 1x1 conv on NHWC data is exactly a GEMM over rows R = N*H*W
 (SURVEY §2c): forward C[R,Cout] = X[R,Cin] x W[Cout,Cin]^T, dgrad uses the
 pre-transposed weight.  Strided (downsample) 1x1 convs gather/scatter the
 even rows around the same GEMMs.  3x3, grouped 3x3 and the generic (stem)
-convs are implicit GEMMs over the same tiles.
+convs are implicit GEMMs over the same tiles.  Stride-1 1x1 convs with thin
+channel counts off the 32 grid (MobileNetV2's 16, 24, 144) run the same
+product on the skinny-GEMM kernel of pwconv.hip instead.
 
 Every weight gradient is tn2_wgrad (wgrad.hip): one launch, split-M fp32
 partials collapsed in a fixed order, so it has no atomics and is bitwise
@@ -232,6 +234,78 @@ def conv1x1_mfma(x: torch.Tensor, weight: torch.Tensor,
     # may hand its compact dgrad to the tap's mailbox
     cell = getattr(x, "_amdtrain_tap_cell", None) if stride == 2 else None
     y, stats = _Conv1x1.apply(x, weight, stride, cell)
+    if stats.numel():
+        y._amdtrain_bn_stats = stats
+    return y
+
+
+def _pwconv_enabled() -> bool:
+    """Thin pointwise kernel (pwconv.hip) for stride-1 1x1 convs off the 32
+    grid; AMDTRAIN_PWCONV=0 restores the routing from before it (generic
+    kernel or MIOpen) for A/B measurement."""
+    return os.environ.get("AMDTRAIN_PWCONV", "1") == "1"
+
+
+def _pw_gemm_ok(k: int, n: int) -> bool:
+    """Host contract of pw_gemm for one orientation: multiples of 8, and the
+    weight zero-padded to 32 x 32 blocks fits 16 KiB of LDS."""
+    return (k >= 8 and n >= 8 and k % 8 == 0 and n % 8 == 0
+            and ((k + 31) // 32) * ((n + 31) // 32) <= 8)
+
+
+def pw_thin_ok(cin: int, cout: int) -> bool:
+    """True when a stride-1 1x1 conv cin -> cout belongs to the thin
+    pointwise kernel: not on the MFMA GEMM's 32 grid, and inside pw_gemm's
+    contract both as forward (K = cin, N = cout) and as input gradient
+    (K = cout, N = cin).  Pure Python; needs no GPU."""
+    if cin % 32 == 0 and cout % 32 == 0:
+        return False
+    return _pw_gemm_ok(cin, cout) and _pw_gemm_ok(cout, cin)
+
+
+class _ConvPw(torch.autograd.Function):
+    """Stride-1 1x1 conv with thin channel counts over pw_gemm
+    (pwconv.hip): forward with the BN-statistics partials as a second,
+    non-differentiable output, input gradient as the same kernel on the
+    transposed weight, weight gradient as tn2_wgrad."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        e = require_ext()
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        xc = x.contiguous(memory_format=torch.channels_last)
+        x2d = _rows(xc)
+        w2d = weight.reshape(cout, cin)
+        y2d, stats = e.pw_gemm(x2d, w2d, _fuse_stats_enabled())
+        ctx.save_for_backward(x2d, w2d)
+        ctx.meta = (n, cin, h, w, cout)
+        y = y2d.view(n, h, w, cout).permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor, _grad_stats=None):
+        e = require_ext()
+        x2d, w2d = ctx.saved_tensors
+        n, cin, h, w, cout = ctx.meta
+        gy = grad_y.contiguous(memory_format=torch.channels_last)
+        gy2d = _rows(gy).to(torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wT = e.transpose_2d(w2d)                  # [Cin, Cout]
+            dx2d = e.pw_gemm(gy2d, wT, False)[0]      # [R, Cin] bf16
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = e.tn2_wgrad(gy2d, x2d).reshape(cout, cin, 1, 1)
+        return dx, dw
+
+
+def conv1x1_thin(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Stride-1 1x1 conv for channel counts inside ``pw_thin_ok``."""
+    y, stats = _ConvPw.apply(x, weight)
     if stats.numel():
         y._amdtrain_bn_stats = stats
     return y
@@ -607,7 +681,10 @@ class AmdConv2d(nn.Conv2d):
     """nn.Conv2d dispatching to the hand-written gfx950 kernels.
 
     State dict / init are identical to nn.Conv2d.  On-GPU bf16 paths:
-    1x1 -> MFMA GEMM (gemm.hip), 3x3 pad-1 s1/s2 -> implicit GEMM
+    1x1 -> MFMA GEMM (gemm.hip), or, stride 1 with channel counts off the
+    32 grid but inside ``pw_thin_ok``, the thin pointwise kernel
+    (pwconv.hip; AMDTRAIN_PWCONV=0 restores the routing from before it),
+    3x3 pad-1 s1/s2 -> implicit GEMM
     (conv3x3.hip), anything else without an input gradient (the 7x7
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
     Depthwise 3x3 pad-1 s1/s2 (groups == in == out channels, C % 8 == 0)
@@ -653,6 +730,14 @@ class AmdConv2d(nn.Conv2d):
                 and self.dilation == (1, 1)):
             ch_ok = (self.in_channels % 32 == 0
                      and self.out_channels % 16 == 0)
+            # thin pointwise: stride-1 1x1 off the 32 grid (pw_thin_ok is
+            # false on it, so every 32-grid layer keeps the GEMM below)
+            if (self.kernel_size == (1, 1) and self.padding == (0, 0)
+                    and self.stride == (1, 1)
+                    and pw_thin_ok(self.in_channels, self.out_channels)
+                    and _pwconv_enabled()
+                    and _conv1x1_env_default() == "custom"):
+                return conv1x1_thin(x, self.weight)
             if (ch_ok and self.kernel_size == (1, 1)
                     and self.padding == (0, 0)
                     and _conv1x1_env_default() == "custom"):

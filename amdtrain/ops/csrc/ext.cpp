@@ -82,6 +82,10 @@ at::Tensor gemm_bt_strided(at::Tensor A, at::Tensor B, long Nn, long H,
 std::vector<at::Tensor> gemm_bt_stats(at::Tensor A, at::Tensor B, long epi);
 at::Tensor transpose_2d(at::Tensor x);
 
+// pwconv.hip
+std::vector<at::Tensor> pw_gemm(at::Tensor A, at::Tensor B, bool want_stats,
+                                long max_blocks);
+
 // conv3x3.hip
 at::Tensor conv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
                        at::Tensor w2d, bool nt64, long epi);
@@ -187,6 +191,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("stride"),
         py::arg("epi") = -1);
   m.def("transpose_2d", &transpose_2d);
+  m.def("pw_gemm", &pw_gemm, py::arg("A"), py::arg("B"),
+        py::arg("want_stats"), py::arg("max_blocks") = -1);
   m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
         py::arg("nt64") = true, py::arg("epi") = -1);

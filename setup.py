@@ -31,6 +31,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "wgrad.hip"),
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "dwconv.hip"),
+        os.path.join(CSRC, "pwconv.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
