@@ -307,8 +307,48 @@ struct MTMeta {
   short chunk_for_block[MT_BLOCKS];
 };
 
+// Layout contract of the multi-tensor ops.  The kernels walk every tensor of
+// a slot (param / grad / momentum, or src / dst) as ONE flat run of numel()
+// elements from data_ptr(), so element i of each must be the same logical
+// element.  That holds iff the tensors have equal sizes, each is
+// non-overlapping and dense, and their strides agree on every dim of size
+// != 1 (a size-1 dim's stride addresses nothing: a channels_last [O,I,1,1]
+// weight and its row-major gradient share one memory order; this is the
+// rule of torch's gradient layout contract).  Anything else would be
+// updated silently permuted or out of bounds, so it is refused here, on the
+// host, before any launch.
+static inline void mt_check_tensor(const char* op, const char* list, size_t i,
+                                   const at::Tensor& t,
+                                   const at::Device& device) {
+  TORCH_CHECK(t.is_cuda() && t.device() == device, op, ": ", list, "[", i,
+              "] is on ", t.device(), ", expected ", device);
+  TORCH_CHECK(t.numel() == 0 || t.is_non_overlapping_and_dense(), op, ": ",
+              list, "[", i, "] is not dense (sizes ", t.sizes(), ", strides ",
+              t.strides(), ")");
+  // chunk_for_block is a short
+  TORCH_CHECK(t.numel() <= 32767 * MT_CHUNK, op, ": ", list, "[", i,
+              "] has too many elements (", t.numel(), ")");
+}
+
+// `t` must share the memory order of `ref` (both already mt_check_tensor'ed)
+static inline void mt_check_same_layout(const char* op, size_t i,
+                                        const char* ref_list,
+                                        const at::Tensor& ref,
+                                        const char* list,
+                                        const at::Tensor& t) {
+  TORCH_CHECK(t.sizes() == ref.sizes(), op, ": ", list, "[", i, "] has sizes ",
+              t.sizes(), " but ", ref_list, "[", i, "] has ", ref.sizes());
+  if (t.numel() == 0) return;
+  for (int64_t d = 0; d < t.dim(); ++d)
+    TORCH_CHECK(t.size(d) == 1 || t.stride(d) == ref.stride(d), op, ": ", list,
+                "[", i, "] has strides ", t.strides(), " but ", ref_list, "[",
+                i, "] has ", ref.strides(), " (sizes ", t.sizes(),
+                "): the tensors of one slot must share a memory order");
+}
+
 // Host-side chunking driver: fills MTMeta over (up to) three parallel tensor
 // lists and invokes `launch(meta, nblocks, ntensors)` for each full batch.
+// Callers validate the lists first (mt_check_tensor / mt_check_same_layout).
 template <typename LaunchFn>
 static void mt_apply(const std::vector<at::Tensor>& A,
                      const std::vector<at::Tensor>* B,

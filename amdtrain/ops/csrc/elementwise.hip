@@ -88,9 +88,11 @@ mt_scale_kernel(MTMeta meta, float scale, float* __restrict__ found_inf) {
   T* __restrict__ p = (T*)meta.b[t];
   bool bad = false;
   for (long i = base + threadIdx.x; i < end; i += blockDim.x) {
-    float v = to_f32(p[i]) * scale;
-    bad |= !isfinite(v);
-    p[i] = from_f32<T>(v);
+    // test the value as stored: an fp32 product that is finite but rounds
+    // to inf in T (fp16: 40000 * 2) must raise the flag too
+    const T r = from_f32<T>(to_f32(p[i]) * scale);
+    bad |= !isfinite(to_f32(r));
+    p[i] = r;
   }
   if (__any(bad) && (threadIdx.x % AMD_WAVE) == 0) *found_inf = 1.f;
 }
@@ -227,6 +229,17 @@ at::Tensor topk_ranks(at::Tensor logits, at::Tensor target) {
 void multi_tensor_scale_check(std::vector<at::Tensor> tensors, double scale,
                               at::Tensor found_inf) {
   if (tensors.empty()) return;
+  const char* op = "multi_tensor_scale_check";
+  const at::Device device = tensors[0].device();
+  TORCH_CHECK(found_inf.is_cuda() && found_inf.device() == device &&
+                  found_inf.scalar_type() == at::kFloat &&
+                  found_inf.numel() >= 1,
+              op, ": found_inf must be a fp32 tensor on ", device);
+  for (size_t i = 0; i < tensors.size(); ++i) {
+    TORCH_CHECK(at::isFloatingType(tensors[i].scalar_type()), op,
+                ": tensors[", i, "] is ", tensors[i].scalar_type());
+    mt_check_tensor(op, "tensors", i, tensors[i], device);
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
   // group by dtype (BN params stay fp32 in the O2 path -> mixed lists)
   std::map<at::ScalarType, std::vector<at::Tensor>> groups;
@@ -249,6 +262,17 @@ void multi_tensor_cast(std::vector<at::Tensor> src,
                        std::vector<at::Tensor> dst) {
   TORCH_CHECK(src.size() == dst.size());
   if (src.empty()) return;
+  const char* op = "multi_tensor_cast";
+  const at::Device device = src[0].device();
+  for (size_t i = 0; i < src.size(); ++i) {
+    TORCH_CHECK(at::isFloatingType(src[i].scalar_type()), op, ": src[", i,
+                "] is ", src[i].scalar_type());
+    TORCH_CHECK(at::isFloatingType(dst[i].scalar_type()), op, ": dst[", i,
+                "] is ", dst[i].scalar_type());
+    mt_check_tensor(op, "src", i, src[i], device);
+    mt_check_tensor(op, "dst", i, dst[i], device);
+    mt_check_same_layout(op, i, "src", src[i], "dst", dst[i]);
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
   std::map<std::pair<at::ScalarType, at::ScalarType>,
            std::pair<std::vector<at::Tensor>, std::vector<at::Tensor>>>

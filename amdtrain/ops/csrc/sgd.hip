@@ -102,9 +102,22 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
   TORCH_CHECK(params.size() == grads.size() &&
               params.size() == momenta.size());
   if (params.empty()) return;
-  for (auto& p : params)
-    TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat,
-                "multi_tensor_sgd expects fp32 CUDA tensors");
+  // every list is checked before the first launch: the kernel reads element
+  // i of param, grad and momentum from the same flat offset
+  const char* op = "multi_tensor_sgd";
+  const at::Device device = params[0].device();
+  for (size_t i = 0; i < params.size(); ++i) {
+    const at::Tensor* slot[3] = {&params[i], &grads[i], &momenta[i]};
+    const char* names[3] = {"params", "grads", "momenta"};
+    for (int k = 0; k < 3; ++k) {
+      TORCH_CHECK(slot[k]->scalar_type() == at::kFloat, op, ": ", names[k],
+                  "[", i, "] is ", slot[k]->scalar_type(),
+                  ", expected fp32 CUDA tensors");
+      mt_check_tensor(op, names[k], i, *slot[k], device);
+      if (k) mt_check_same_layout(op, i, names[0], params[i], names[k],
+                                  *slot[k]);
+    }
+  }
   SGDArgs args{(float)lr, (float)momentum, (float)weight_decay, nesterov,
                first, zero_grad};
   auto stream = at::cuda::getCurrentCUDAStream();

@@ -22,6 +22,7 @@ __all__ = [
     "ext", "ext_available", "require_ext", "use_ext_for",
     "cross_entropy", "topk_correct_counts", "normalize_u8",
     "multi_tensor_scale_check", "multi_tensor_cast",
+    "mt_dense", "mt_same_layout",
 ]
 
 
@@ -115,15 +116,58 @@ def normalize_u8(x: torch.Tensor, dtype: torch.dtype = torch.float32,
 # Multi-tensor loss-scale / unscale + inf check and dtype casts
 # (apex amp_C equivalents, apex_distributed.py:216,328-329; horovod fp16
 # gradient compression, horovod_distributed.py:159).
+#
+# Layout contract: the multi-tensor kernels walk every tensor as one flat
+# run of numel() elements from data_ptr().  The tensors of one slot (param /
+# grad / momentum, src / dst) must therefore have equal sizes, be
+# non-overlapping and dense, and agree in stride on every dim of size != 1.
+# ``_C`` refuses anything else; the wrappers here (and FusedSGD.step) route
+# such tensors to per-tensor torch ops, which index logically.
 # --------------------------------------------------------------------------
+
+def mt_dense(t: torch.Tensor) -> bool:
+    """Non-overlapping and dense: the storage span holds numel() elements."""
+    if t.is_contiguous() or t.numel() == 0:
+        return True
+    if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
+        return True
+    # any other permutation: walking the dims by ascending stride, each
+    # stride must equal the product of the sizes already passed
+    expect = 1
+    for stride, size in sorted((st, s) for s, st in zip(t.shape, t.stride())
+                               if s != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def mt_same_layout(ref: torch.Tensor, *others: torch.Tensor) -> bool:
+    """True when ``others`` can share one flat index with ``ref``."""
+    if not mt_dense(ref):
+        return False
+    shape, strides = ref.shape, ref.stride()
+    for t in others:
+        if t.shape != shape:
+            return False
+        ts = t.stride()
+        if ts != strides and any(
+                n != 1 and a != b for n, a, b in zip(shape, ts, strides)):
+            return False
+    return True
+
 
 def multi_tensor_scale_check(tensors: List[torch.Tensor], scale: float,
                              found_inf: torch.Tensor) -> None:
     """In-place: t *= scale for each tensor; set found_inf[0]=1 on inf/nan."""
+    loop = tensors
     if tensors and tensors[0].is_cuda and ext_available():
-        require_ext().multi_tensor_scale_check(tensors, scale, found_inf)
-        return
-    for t in tensors:
+        ok = [mt_dense(t) for t in tensors]
+        fused = [t for t, k in zip(tensors, ok) if k]
+        loop = [t for t, k in zip(tensors, ok) if not k]
+        if fused:
+            require_ext().multi_tensor_scale_check(fused, scale, found_inf)
+    for t in loop:
         t.mul_(scale)
         if not torch.isfinite(t).all():
             found_inf.fill_(1.0)
@@ -131,8 +175,13 @@ def multi_tensor_scale_check(tensors: List[torch.Tensor], scale: float,
 
 def multi_tensor_cast(src: List[torch.Tensor], dst: List[torch.Tensor]) -> None:
     """dst[i].copy_(src[i]) with dtype conversion, one fused launch on GPU."""
+    loop = list(zip(src, dst))
     if src and src[0].is_cuda and ext_available():
-        require_ext().multi_tensor_cast(src, dst)
-        return
-    for s, d in zip(src, dst):
+        ok = [mt_same_layout(s, d) for s, d in zip(src, dst)]
+        loop = [sd for sd, k in zip(loop, ok) if not k]
+        if len(loop) != len(src):
+            require_ext().multi_tensor_cast(
+                [s for s, k in zip(src, ok) if k],
+                [d for d, k in zip(dst, ok) if k])
+    for s, d in loop:
         d.copy_(s)

@@ -19,6 +19,7 @@ import torch
 from torch.optim import Optimizer
 
 from ._ext import ext_available, require_ext
+from .functional import mt_same_layout
 
 
 class FusedSGD(Optimizer):
@@ -32,6 +33,13 @@ class FusedSGD(Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening,
                         weight_decay=weight_decay, nesterov=nesterov)
         super().__init__(params, defaults)
+        # which route the param groups of the most recent step() took: the
+        # fused multi-tensor kernel, or the per-tensor loop (CPU tensors,
+        # dampening, mixed first-step state, or a (param, grad, buffer)
+        # triple that does not share one memory order — the kernel indexes
+        # all three flat, see ops/functional.py "Layout contract")
+        self.last_step_fused = 0
+        self.last_step_loop = 0
 
     @torch.no_grad()
     def step(self, closure=None, zero_grad: bool = False):
@@ -40,6 +48,8 @@ class FusedSGD(Optimizer):
             with torch.enable_grad():
                 loss = closure()
 
+        self.last_step_fused = 0
+        self.last_step_loop = 0
         for group in self.param_groups:
             params: List[torch.Tensor] = []
             grads: List[torch.Tensor] = []
@@ -62,9 +72,11 @@ class FusedSGD(Optimizer):
             if not params:
                 continue
 
-            fused_ok = (params[0].is_cuda and ext_available()
+            fused_ok = (self._ext_serves(params)
                         and group["dampening"] == 0
-                        and all(f == firsts[0] for f in firsts))
+                        and all(f == firsts[0] for f in firsts)
+                        and all(mt_same_layout(p, g, b)
+                                for p, g, b in zip(params, grads, bufs)))
             if fused_ok:
                 require_ext().multi_tensor_sgd(
                     params, grads, bufs,
@@ -72,9 +84,15 @@ class FusedSGD(Optimizer):
                     float(group["weight_decay"]), bool(group["nesterov"]),
                     bool(firsts[0] and group["momentum"] != 0),
                     bool(zero_grad))
+                self.last_step_fused += 1
             else:
                 self._step_loop(group, params, grads, firsts, zero_grad)
+                self.last_step_loop += 1
         return loss
+
+    @staticmethod
+    def _ext_serves(params) -> bool:
+        return params[0].is_cuda and ext_available()
 
     def _step_loop(self, group, params, grads, firsts, zero_grad):
         mu, damp = group["momentum"], group["dampening"]

@@ -131,7 +131,10 @@ class ScatterGatherDataParallel(nn.Module):
             if extra is None:
                 continue
             if p.grad is None:
-                p.grad = extra.clone()
+                # `extra` is a row-major piece of the flat transfer; the grad
+                # takes the param's memory order (gradient layout contract,
+                # which the fused optimizer relies on)
+                p.grad = torch.empty_like(p).copy_(extra)
             else:
                 p.grad.add_(extra)
 

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from ..comm.collectives import broadcast_module_state
 from ..comm.init import is_distributed
-from .reducer import BucketedReducer
+from .reducer import BucketedReducer, view_like
 
 
 class NativeDDP(nn.Module):
@@ -58,7 +58,8 @@ class NativeDDP(nn.Module):
             off = 0
             for mod, name, buf in items:
                 n = buf.numel()
-                view = flat[off:off + n].view_as(buf)
+                # in buf's own memory order, like the reducer's grad views
+                view = view_like(flat[off:off + n], buf)
                 view.copy_(buf)
                 mod._buffers[name] = view
                 off += n

@@ -36,6 +36,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from ..ops import functional as OF
+
 
 class _Bucket:
     __slots__ = ("params", "flat", "comm_buf", "ready", "work", "index")
@@ -48,6 +50,25 @@ class _Bucket:
         self.comm_buf = comm_buf  # half-precision staging when compressing
         self.ready = 0
         self.work = None
+
+
+def view_like(piece: torch.Tensor, p: torch.Tensor) -> torch.Tensor:
+    """View of the flat bucket slice ``piece`` (numel == p.numel()) shaped
+    like ``p``, in ``p``'s own memory order.
+
+    A channels_last conv weight must get a channels_last gradient: autograd
+    accumulates in place and keeps whatever strides the view has, and the
+    fused optimizer indexes param, grad and momentum by one flat offset
+    (torch's gradient layout contract; ops/functional.py "Layout contract").
+    A dense param's strides address exactly numel() elements, so they fit
+    the slice; any other param gets the row-major view and the optimizer's
+    per-tensor route.  The all-reduce, the compression copies and zero_grad
+    work on the flat buffer and do not care; every rank holds the same
+    model, so every rank builds the same layout.
+    """
+    if OF.mt_dense(p):
+        return piece.as_strided(p.size(), p.stride())
+    return piece.view_as(p)
 
 
 class BucketedReducer:
@@ -110,7 +131,7 @@ class BucketedReducer:
             off = 0
             for p in group:
                 n = p.numel()
-                p.grad = flat[off:off + n].view_as(p)
+                p.grad = view_like(flat[off:off + n], p)
                 off += n
                 self.param_to_bucket[p] = bucket
             self.buckets.append(bucket)

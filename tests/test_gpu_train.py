@@ -74,6 +74,8 @@ def test_native_ddp_world1_gpu():
         loss = crit(out, t)
         loss.backward()
         opt.step()
+        # bucket-view grads carry the params' strides: still the fused route
+        assert (opt.last_step_fused, opt.last_step_loop) == (1, 0)
     torch.cuda.synchronize()
     assert torch.isfinite(loss).item()
 
@@ -342,6 +344,10 @@ def test_training_bitwise_deterministic():
                 loss = crit(m(x), t)
             loss.backward()
             opt.step()
+            # single-process grads obey the multi-tensor layout contract:
+            # every param group takes the fused kernel, none the loop
+            assert (opt.last_step_fused, opt.last_step_loop) == \
+                (len(opt.param_groups), 0)
         torch.cuda.synchronize()
         return torch.cat([p.detach().reshape(-1).float()
                           for p in m.parameters()])
