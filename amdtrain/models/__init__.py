@@ -8,6 +8,8 @@ from .resnet import (
     resnet101,
     resnet152,
     resnext50_32x4d,
+    resnext101_32x8d,
+    resnext101_64x4d,
     wide_resnet50_2,
 )
 from .mobilenet import MobileNetV2, InvertedResidual, mobilenet_v2
@@ -16,6 +18,7 @@ from .registry import build_model, model_names
 __all__ = [
     "ResNet", "BasicBlock", "Bottleneck", "build_model", "model_names",
     "resnet18", "resnet34", "resnet50", "resnet101", "resnet152",
-    "resnext50_32x4d", "wide_resnet50_2",
+    "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d",
+    "wide_resnet50_2",
     "MobileNetV2", "InvertedResidual", "mobilenet_v2",
 ]

@@ -9,7 +9,8 @@ import torch.nn as nn
 
 from .mobilenet import mobilenet_v2
 from .resnet import (resnet18, resnet34, resnet50, resnet101, resnet152,
-                     resnext50_32x4d, wide_resnet50_2)
+                     resnext50_32x4d, resnext101_32x8d, resnext101_64x4d,
+                     wide_resnet50_2)
 
 _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "resnet18": resnet18,
@@ -18,6 +19,8 @@ _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "resnet101": resnet101,
     "resnet152": resnet152,
     "resnext50_32x4d": resnext50_32x4d,
+    "resnext101_32x8d": resnext101_32x8d,
+    "resnext101_64x4d": resnext101_64x4d,
     "wide_resnet50_2": wide_resnet50_2,
     "mobilenet_v2": mobilenet_v2,
 }

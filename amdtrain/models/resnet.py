@@ -250,6 +250,16 @@ def resnext50_32x4d(num_classes: int = 1000, **kw) -> ResNet:
                   groups=32, width_per_group=4, **kw)
 
 
+def resnext101_32x8d(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes,
+                  groups=32, width_per_group=8, **kw)
+
+
+def resnext101_64x4d(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes,
+                  groups=64, width_per_group=4, **kw)
+
+
 def wide_resnet50_2(num_classes: int = 1000, **kw) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes=num_classes,
                   width_per_group=128, **kw)

@@ -370,6 +370,34 @@ def conv3x3_mfma(x: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+def _grouped_dw(e, gy2d, x2d, n, h, w, stride, cout, groups, banded):
+    """Weight gradient [Cout, S, 3, 3] (channels_last) of a grouped 3x3
+    conv, shared by both grouped paths: ``banded`` (Cin == Cout, both
+    % 128) the banded tn2 wgrad plus the group diagonal of each
+    128-channel window, else the dense tn2 wgrad plus the group diagonal of
+    the dense dW."""
+    cin = x2d.shape[1]
+    sg = cin // groups
+    sout = cout // groups
+    if banded:
+        # compact band [Cout, 9, 128]: extract the group diagonal of
+        # each 128-channel window
+        dwb = e.tn2_wgrad_banded(gy2d, x2d, n, h, w, stride) \
+            .view(cout // 128, 128 // sg, sg, 9, 128 // sg, sg)
+        bi = torch.arange(cout // 128, device=dwb.device)[:, None]
+        gi = torch.arange(128 // sg, device=dwb.device)[None, :]
+        return dwb[bi, gi, :, :, gi, :].reshape(cout, 9, sg) \
+            .view(cout, 3, 3, sg).permute(0, 3, 1, 2) \
+            .contiguous(memory_format=torch.channels_last)
+    dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2)
+    # slice the group diagonal of the dense dW
+    dwd = dw2d.view(groups, sout, 3, 3, groups, sg)
+    gi = torch.arange(groups, device=dwd.device)
+    return dwd[gi, :, :, :, gi, :].permute(0, 1, 4, 2, 3) \
+        .reshape(cout, sg, 3, 3) \
+        .contiguous(memory_format=torch.channels_last)
+
+
 class _ConvGrouped3x3(torch.autograd.Function):
     """Grouped 3x3 conv (ResNeXt) as a BLOCK-DIAGONALIZED dense conv over
     the in-house implicit-GEMM kernels.
@@ -428,38 +456,83 @@ class _ConvGrouped3x3(torch.autograd.Function):
         e = require_ext()
         x2d, w2d = ctx.saved_tensors
         n, cin, h, w, stride, cout, groups, banded = ctx.meta
-        sg = cin // groups
-        sout = cout // groups
         gy = grad_y.contiguous(memory_format=torch.channels_last)
         gy2d = _rows(gy).to(torch.bfloat16)
         dx2d = e.conv3x3_dgrad(gy2d, n, h, w, stride, w2d, banded,
                                _s2parity_enabled(), _nt64_enabled(),
                                _epilogue_mode())
         dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        if banded:
-            # compact band [Cout, 9, 128]: extract the group diagonal of
-            # each 128-channel window
-            dwb = e.tn2_wgrad_banded(gy2d, x2d, n, h, w, stride) \
-                .view(cout // 128, 128 // sg, sg, 9, 128 // sg, sg)
-            bi = torch.arange(cout // 128, device=dwb.device)[:, None]
-            gi = torch.arange(128 // sg, device=dwb.device)[None, :]
-            dw = dwb[bi, gi, :, :, gi, :].reshape(cout, 9, sg) \
-                .view(cout, 3, 3, sg).permute(0, 3, 1, 2) \
-                .contiguous(memory_format=torch.channels_last)
-            return dx, dw, None, None
-        dw2d = e.tn2_wgrad(gy2d, x2d, 9, n, h, w, stride, 2)
-        # slice the group diagonal of the dense dW
-        dwd = dw2d.view(groups, sout, 3, 3, groups, sg)
-        gi = torch.arange(groups, device=dwd.device)
-        dw = dwd[gi, :, :, :, gi, :].permute(0, 1, 4, 2, 3) \
-            .reshape(cout, sg, 3, 3) \
-            .contiguous(memory_format=torch.channels_last)
+        dw = _grouped_dw(e, gy2d, x2d, n, h, w, stride, cout, groups, banded)
         return dx, dw, None, None
 
 
 def conv3x3_grouped_mfma(x: torch.Tensor, weight: torch.Tensor,
                          stride: int, groups: int) -> torch.Tensor:
     y, stats = _ConvGrouped3x3.apply(x, weight, stride, groups)
+    if stats.numel():
+        y._amdtrain_bn_stats = stats
+    return y
+
+
+def _gconv_enabled() -> bool:
+    """Per-group kernel (gconv.hip) for grouped 3x3 convs inside
+    ``gconv_ok``; AMDTRAIN_GCONV=0 keeps the banded dense path."""
+    return os.environ.get("AMDTRAIN_GCONV", "1") != "0"
+
+
+def gconv_ok(cin: int, cout: int, groups: int) -> bool:
+    """Contract of the per-group kernel: Cin == Cout on the 32 grid and 4,
+    8, 16 or 32 channels per group.  Pure Python; needs no GPU."""
+    return (cin == cout and cin % 32 == 0 and cin % groups == 0
+            and cin // groups in (4, 8, 16, 32))
+
+
+class _GConv3x3(torch.autograd.Function):
+    """Grouped 3x3 pad-1 conv (stride 1/2) over the per-group MFMA kernel of
+    gconv.hip: one pack launch per direction instead of the dense weight
+    expansion, forward with the BN-statistics partials, input gradient as
+    the same kernel over dY.  The weight gradient is the banded / dense
+    tn2 wgrad of ``_ConvGrouped3x3`` (``_grouped_dw``)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int,
+                groups: int):
+        e = require_ext()
+        n, c, h, w = x.shape
+        xc = x.contiguous(memory_format=torch.channels_last)
+        x2d = _rows(xc)
+        packed = e.gconv3x3_pack(weight, groups, False)
+        y2d, stats = e.gconv3x3_fwd(x2d, n, h, w, stride, packed, groups,
+                                    _fuse_stats_enabled())
+        ctx.save_for_backward(x2d, weight)
+        ctx.meta = (n, c, h, w, stride, groups)
+        ho = (h + 2 - 3) // stride + 1
+        wo = (w + 2 - 3) // stride + 1
+        y = y2d.view(n, ho, wo, c).permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor, _grad_stats=None):
+        e = require_ext()
+        x2d, weight = ctx.saved_tensors
+        n, c, h, w, stride, groups = ctx.meta
+        gy = grad_y.contiguous(memory_format=torch.channels_last)
+        gy2d = _rows(gy).to(torch.bfloat16)
+        packed = e.gconv3x3_pack(weight, groups, True)
+        dx2d = e.gconv3x3_dgrad(gy2d, n, h, w, stride, packed, groups)
+        dx = dx2d.view(n, h, w, c).permute(0, 3, 1, 2)
+        dw = _grouped_dw(e, gy2d, x2d, n, h, w, stride, c, groups,
+                         c % 128 == 0)
+        return dx, dw, None, None
+
+
+def conv3x3_grouped(x: torch.Tensor, weight: torch.Tensor, stride: int,
+                    groups: int) -> torch.Tensor:
+    """Grouped 3x3 pad-1 conv inside ``gconv_ok`` on the per-group kernel."""
+    y, stats = _GConv3x3.apply(x, weight, stride, groups)
     if stats.numel():
         y._amdtrain_bn_stats = stats
     return y
@@ -689,7 +762,9 @@ class AmdConv2d(nn.Conv2d):
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
     Depthwise 3x3 pad-1 s1/s2 (groups == in == out channels, C % 8 == 0)
     -> vectorised stencil (dwconv.hip); other grouped 3x3 with
-    in % 32 == 0 and out % 16 == 0 (ResNeXt) -> block-diagonalized dense
+    in % 32 == 0 and out % 16 == 0 (ResNeXt) -> the per-group MFMA kernel
+    (gconv.hip) when in == out and in / groups is 4, 8, 16 or 32
+    (AMDTRAIN_GCONV=0 switches it off), else the block-diagonalized dense
     conv3x3.  Every other grouped conv, dilated convs, convs with a bias
     and fp32 inference fall through to MIOpen.
     Env overrides AMDTRAIN_CONV1X1 / AMDTRAIN_CONV3X3 / AMDTRAIN_CONV3X3G /
@@ -714,7 +789,8 @@ class AmdConv2d(nn.Conv2d):
                 if os.environ.get("AMDTRAIN_DWCONV", "custom") == "miopen":
                     return super().forward(x)
                 return dwconv3x3(x, self.weight, self.stride[0])
-            # grouped 3x3 (ResNeXt): block-diagonalized dense path
+            # grouped 3x3 (ResNeXt): per-group kernel inside its contract,
+            # block-diagonalized dense path otherwise
             if (self.kernel_size == (3, 3) and self.padding == (1, 1)
                     and self.stride[0] in (1, 2)
                     and self.in_channels % 32 == 0
@@ -722,6 +798,10 @@ class AmdConv2d(nn.Conv2d):
                     and self.in_channels % self.groups == 0
                     and os.environ.get("AMDTRAIN_CONV3X3G", "custom")
                     == "custom"):
+                if (gconv_ok(self.in_channels, self.out_channels,
+                             self.groups) and _gconv_enabled()):
+                    return conv3x3_grouped(x, self.weight, self.stride[0],
+                                           self.groups)
                 return conv3x3_grouped_mfma(x, self.weight, self.stride[0],
                                             self.groups)
             return super().forward(x)

@@ -97,6 +97,15 @@ at::Tensor conv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
                          long stride, at::Tensor w2d, bool banded,
                          bool s2parity, bool nt64, long epi);
 
+// gconv.hip (grouped 3x3, Cin == Cout, S = C / groups in {4, 8, 16, 32};
+// H, W are the input's, also for the dgrad)
+at::Tensor gconv3x3_pack(at::Tensor weight, long groups, bool dgrad);
+std::vector<at::Tensor> gconv3x3_fwd(at::Tensor x2d, long Nn, long H, long W,
+                                     long stride, at::Tensor packed,
+                                     long groups, bool want_stats);
+at::Tensor gconv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
+                          long stride, at::Tensor packed, long groups);
+
 // gemm8p.hip
 at::Tensor gemm_bt_8p3(at::Tensor A, at::Tensor B);
 
@@ -207,6 +216,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
         py::arg("banded") = false, py::arg("s2parity") = true,
         py::arg("nt64") = true, py::arg("epi") = -1);
+  m.def("gconv3x3_pack", &gconv3x3_pack, py::arg("weight"),
+        py::arg("groups"), py::arg("dgrad"));
+  m.def("gconv3x3_fwd", &gconv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("packed"),
+        py::arg("groups"), py::arg("want_stats"));
+  m.def("gconv3x3_dgrad", &gconv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("packed"),
+        py::arg("groups"));
   m.def("tn2_wgrad", &tn2_wgrad, py::arg("dY"), py::arg("X"),
         py::arg("taps") = 1, py::arg("Nn") = 0, py::arg("H") = 0,
         py::arg("W") = 0, py::arg("stride") = 1, py::arg("gmode") = 0,
