@@ -480,6 +480,13 @@ def _gconv_enabled() -> bool:
     return os.environ.get("AMDTRAIN_GCONV", "1") != "0"
 
 
+def _gconv_wgrad_enabled() -> bool:
+    """Per-group weight-gradient kernel (gconv_wgrad.hip) inside
+    ``_GConv3x3``; AMDTRAIN_GCONV_WGRAD=0 keeps the banded / dense tn2 wgrad
+    with the eager diagonal extraction (``_grouped_dw``)."""
+    return os.environ.get("AMDTRAIN_GCONV_WGRAD", "1") != "0"
+
+
 def gconv_ok(cin: int, cout: int, groups: int) -> bool:
     """Contract of the per-group kernel: Cin == Cout on the 32 grid and 4,
     8, 16 or 32 channels per group.  Pure Python; needs no GPU."""
@@ -491,8 +498,9 @@ class _GConv3x3(torch.autograd.Function):
     """Grouped 3x3 pad-1 conv (stride 1/2) over the per-group MFMA kernel of
     gconv.hip: one pack launch per direction instead of the dense weight
     expansion, forward with the BN-statistics partials, input gradient as
-    the same kernel over dY.  The weight gradient is the banded / dense
-    tn2 wgrad of ``_ConvGrouped3x3`` (``_grouped_dw``)."""
+    the same kernel over dY.  The weight gradient is the per-group kernel of
+    gconv_wgrad.hip, or with AMDTRAIN_GCONV_WGRAD=0 the banded / dense tn2
+    wgrad of ``_ConvGrouped3x3`` (``_grouped_dw``)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
@@ -524,8 +532,11 @@ class _GConv3x3(torch.autograd.Function):
         packed = e.gconv3x3_pack(weight, groups, True)
         dx2d = e.gconv3x3_dgrad(gy2d, n, h, w, stride, packed, groups)
         dx = dx2d.view(n, h, w, c).permute(0, 3, 1, 2)
-        dw = _grouped_dw(e, gy2d, x2d, n, h, w, stride, c, groups,
-                         c % 128 == 0)
+        if _gconv_wgrad_enabled():
+            dw = e.gconv3x3_wgrad(gy2d, x2d, n, h, w, stride, groups)
+        else:
+            dw = _grouped_dw(e, gy2d, x2d, n, h, w, stride, c, groups,
+                             c % 128 == 0)
         return dx, dw, None, None
 
 

@@ -106,6 +106,10 @@ std::vector<at::Tensor> gconv3x3_fwd(at::Tensor x2d, long Nn, long H, long W,
 at::Tensor gconv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
                           long stride, at::Tensor packed, long groups);
 
+// gconv_wgrad.hip (same contract; returns dW [C, S, 3, 3] fp32 channels_last)
+at::Tensor gconv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
+                          long W, long stride, long groups, long nsplit);
+
 // gemm8p.hip
 at::Tensor gemm_bt_8p3(at::Tensor A, at::Tensor B);
 
@@ -224,7 +228,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gconv3x3_dgrad", &gconv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("packed"),
         py::arg("groups"));
-  m.def("tn2_wgrad", &tn2_wgrad, py::arg("dY"), py::arg("X"),
+  m.def("gconv3x3_wgrad", &gconv3x3_wgrad, py::arg("dy2d"), py::arg("x2d"),
+        py::arg("Nn"), py::arg("H"), py::arg("W"), py::arg("stride"),
+        py::arg("groups"), py::arg("nsplit") = 0);
+  m.def("tn2_wgrad",&tn2_wgrad, py::arg("dY"), py::arg("X"),
         py::arg("taps") = 1, py::arg("Nn") = 0, py::arg("H") = 0,
         py::arg("W") = 0, py::arg("stride") = 1, py::arg("gmode") = 0,
         py::arg("kh") = 3, py::arg("kw") = 3, py::arg("pad") = 1,

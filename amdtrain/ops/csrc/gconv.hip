@@ -308,8 +308,9 @@ gconv_pack_kernel(const bf16* __restrict__ w, bf16* __restrict__ out, int C,
 #pragma clang attribute pop
 #endif
 
-// contract shared by the three entry points: C % 32 == 0, S in {4,8,16,32}
-static int gconv_window(long C, long groups, const char* op) {
+// contract shared by the entry points here and in gconv_wgrad.hip:
+// C % 32 == 0, S in {4,8,16,32}
+int gconv_window(long C, long groups, const char* op) {
   TORCH_CHECK(groups > 0 && C % 32 == 0 && C % groups == 0, op,
               ": C must be a multiple of 32 and of groups, got C = ", C,
               ", groups = ", groups);

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "gemm.hip"),
         os.path.join(CSRC, "conv3x3.hip"),
         os.path.join(CSRC, "gconv.hip"),
+        os.path.join(CSRC, "gconv_wgrad.hip"),
         os.path.join(CSRC, "conv_stem.hip"),
         os.path.join(CSRC, "gemm8p.hip"),
         os.path.join(CSRC, "wgrad.hip"),

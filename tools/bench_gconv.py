@@ -1,8 +1,10 @@
 """Grouped 3x3 convs of resnext50_32x4d at batch 256: per-call time of the
-forward with statistics and of the input gradient, per-group kernel
-(gconv.hip) against the banded dense path, each with its own weight
-preparation as a training step pays it (one pack launch / the eager dense
-expansion).  The two are alternated in one process and compared.
+forward with statistics, of the input gradient and of the weight gradient,
+per-group kernels (gconv.hip, gconv_wgrad.hip) against the banded dense path,
+each with what a training step pays around it (one pack launch / the eager
+dense expansion; for the banded weight gradient the eager extraction of the
+group diagonal).  The two are alternated in one process and compared.
+``AMDTRAIN_BENCH_NSPLIT`` forces the weight-gradient kernel's split.
 
 Without arguments every shape runs in a child process of its own under a
 time limit, and the run stops at the first child that fails;
@@ -35,6 +37,8 @@ def time_fn(fn, iters=20):
 def run(idx):
     import torch
     from amdtrain import _C
+    from amdtrain.ops.conv import _grouped_dw
+    nsplit = int(os.environ.get("AMDTRAIN_BENCH_NSPLIT", "0"))
     cnt, c, hw, stride = SHAPES[idx]
     n, s = BATCH, c // GROUPS
     ho = (hw + 2 - 3) // stride + 1
@@ -65,7 +69,12 @@ def run(idx):
                                                True),
             "group": lambda: _C.gconv3x3_dgrad(
                 gy2d, n, hw, hw, stride, _C.gconv3x3_pack(w, GROUPS, True),
-                GROUPS)}}
+                GROUPS)},
+        "wgrad": {
+            "banded": lambda: _grouped_dw(_C, gy2d, x2d, n, hw, hw, stride, c,
+                                          GROUPS, True),
+            "group": lambda: _C.gconv3x3_wgrad(gy2d, x2d, n, hw, hw, stride,
+                                               GROUPS, nsplit)}}
     # bytes the op must move (read + write once) and the flops it contains
     byts = 2.0 * c * n * (hw * hw + ho * ho)
     flops = 2.0 * n * ho * ho * c * 9 * s
