@@ -20,7 +20,7 @@ from ..data.build import build_loaders
 from ..data.prefetcher import CudaPrefetcher
 from ..engine.loops import TrainState, train, validate
 from ..models import build_model
-from ..ops import CrossEntropyLoss, FusedSGD
+from ..ops import CrossEntropyLoss, FusedLARS, FusedSGD
 from ..parallel import NativeDDP, DistributedOptimizer, Compression, amp
 from ..utils import (adjust_learning_rate, load_checkpoint, save_checkpoint,
                      set_seed)
@@ -50,6 +50,27 @@ def select_device(local_rank: int) -> torch.device:
     return torch.device("cpu")
 
 
+def build_optimizer(args, params):
+    """The optimizer --optimizer names, over ``params``."""
+    if args.optimizer == "lars":
+        return FusedLARS(params, args.lr, momentum=args.momentum,
+                         weight_decay=args.weight_decay,
+                         trust_coefficient=args.trust_coefficient)
+    return FusedSGD(params, args.lr, momentum=args.momentum,
+                    weight_decay=args.weight_decay)
+
+
+def warmup_state(args, train_loader) -> dict:
+    """TrainState fields of --warmup-epochs (empty when warm-up is off)."""
+    if not args.warmup_epochs:
+        return {}
+    iters = len(train_loader)
+    if args.max_steps:
+        iters = min(iters, args.max_steps)
+    return dict(warmup_epochs=args.warmup_epochs, base_lr=args.lr,
+                iters_per_epoch=iters)
+
+
 def run_worker(local_rank: int, nprocs: int, args, style: StyleConfig,
                global_rank: Optional[int] = None) -> float:
     """Train/evaluate on one rank.  Returns best top-1."""
@@ -69,9 +90,7 @@ def run_worker(local_rank: int, nprocs: int, args, style: StyleConfig,
     args.batch_size = max(1, args.batch_size // max(nprocs, 1))
 
     criterion = CrossEntropyLoss().to(device)
-    optimizer = FusedSGD(model.parameters(), args.lr,
-                         momentum=args.momentum,
-                         weight_decay=args.weight_decay)
+    optimizer = build_optimizer(args, model.parameters())
 
     autocast_dtype = _DTYPES[args.dtype] if device.type == "cuda" else None
 
@@ -120,6 +139,7 @@ def run_worker(local_rank: int, nprocs: int, args, style: StyleConfig,
         data_dtype=data_dtype,
         print_freq=args.print_freq,
         max_steps=args.max_steps,
+        **warmup_state(args, train_loader),
     )
 
     if args.evaluate:

@@ -16,11 +16,12 @@ from ..config import base_parser
 from ..data.build import build_loaders
 from ..engine.loops import TrainState, train, validate
 from ..models import build_model
-from ..ops import CrossEntropyLoss, FusedSGD
+from ..ops import CrossEntropyLoss
 from ..parallel import ScatterGatherDataParallel
 from ..utils import adjust_learning_rate, save_checkpoint, set_seed
 from ..utils.checkpoint import make_checkpoint_state
 from ..utils.csvlog import EpochTimer
+from .common import build_optimizer, warmup_state
 
 
 def parse_args(argv=None):
@@ -51,8 +52,7 @@ def main(argv=None) -> float:
         model = ScatterGatherDataParallel(model, gpus, output_device=gpus[0])
 
     criterion = CrossEntropyLoss().to(device)
-    optimizer = FusedSGD(model.parameters(), args.lr, momentum=args.momentum,
-                         weight_decay=args.weight_decay)
+    optimizer = build_optimizer(args, model.parameters())
 
     # full-node batch, plain shuffled loader (reference :165-169)
     train_loader, val_loader, _, _ = build_loaders(args, world_size=1, rank=0,
@@ -63,7 +63,8 @@ def main(argv=None) -> float:
         autocast_dtype={"fp32": None, "bf16": torch.bfloat16,
                         "fp16": torch.float16}[args.dtype]
         if device.type == "cuda" else None,
-        print_freq=args.print_freq, max_steps=args.max_steps)
+        print_freq=args.print_freq, max_steps=args.max_steps,
+        **warmup_state(args, train_loader))
 
     if args.evaluate:
         return validate(val_loader, model, criterion, state)

@@ -71,4 +71,12 @@ def base_parser(description: str) -> argparse.ArgumentParser:
                    help="append per-epoch wall-clock seconds to this CSV")
     p.add_argument("--max-steps", default=0, type=int,
                    help="cap steps per epoch (quick runs / tests)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="sgd: fused momentum SGD; lars: fused layer-wise "
+                        "adaptive rate scaling for large global batches")
+    p.add_argument("--trust-coefficient", default=0.001, type=float,
+                   help="LARS trust coefficient (default: 0.001)")
+    p.add_argument("--warmup-epochs", default=0, type=int, metavar="N",
+                   help="linear LR warm-up from 0 to --lr over the first N "
+                        "epochs, stepped per iteration (default: 0 = off)")
     return p

@@ -25,6 +25,7 @@ import torch
 
 from ..comm.collectives import MetricReducer
 from ..parallel import amp as amp_mod
+from ..utils.lr import warmup_learning_rate
 from ..utils.meters import AverageMeter, ProgressMeter
 from ..utils.metrics import accuracy
 
@@ -40,6 +41,10 @@ class TrainState:
     data_dtype: Optional[torch.dtype] = None      # activation input dtype
     print_freq: int = 10
     max_steps: int = 0               # 0 = full epoch
+    # linear LR warm-up (utils/lr.py), stepped per iteration; 0 = off
+    warmup_epochs: int = 0
+    base_lr: float = 0.0
+    iters_per_epoch: int = 0         # a prefetcher has no len()
 
     def input_dtype(self) -> torch.dtype:
         return self.data_dtype or self.autocast_dtype or torch.float32
@@ -105,6 +110,9 @@ def train(loader, model, criterion, optimizer, epoch: int,
             break
         images, target = _to_device(batch, state)
         data_time.update(time.time() - end)
+        if state.warmup_epochs:
+            warmup_learning_rate(optimizer, epoch, i, state.iters_per_epoch,
+                                 state.base_lr, state.warmup_epochs)
 
         with _autocast(state, model):
             output = model(images)

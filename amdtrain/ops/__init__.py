@@ -13,6 +13,8 @@ On a GPU box, ops raise if the extension is missing unless
 from . import functional  # noqa: F401
 from . import fused  # noqa: F401
 from .sgd import FusedSGD  # noqa: F401
+from .lars import FusedLARS  # noqa: F401
 from .cross_entropy import CrossEntropyLoss  # noqa: F401
 
-__all__ = ["functional", "fused", "FusedSGD", "CrossEntropyLoss"]
+__all__ = ["functional", "fused", "FusedSGD", "FusedLARS",
+           "CrossEntropyLoss"]

@@ -349,12 +349,23 @@ static inline void mt_check_same_layout(const char* op, size_t i,
 // Host-side chunking driver: fills MTMeta over (up to) three parallel tensor
 // lists and invokes `launch(meta, nblocks, ntensors)` for each full batch.
 // Callers validate the lists first (mt_check_tensor / mt_check_same_layout).
+// A `launch` that takes a fourth argument (size_t) also receives the list
+// index of the tensor in slot 0; slot s then holds list entry first + s (an
+// op with per-tensor side data, lars.hip, finds its rows by it).
 template <typename LaunchFn>
 static void mt_apply(const std::vector<at::Tensor>& A,
                      const std::vector<at::Tensor>* B,
-                     const std::vector<at::Tensor>* C, LaunchFn launch) {
+                     const std::vector<at::Tensor>* C, LaunchFn user_launch) {
   MTMeta meta;
   int t = 0, blk = 0;
+  size_t first = 0;
+  auto launch = [&](const MTMeta& m, int blocks, int tensors) {
+    if constexpr (std::is_invocable_v<LaunchFn&, const MTMeta&, int, int,
+                                      size_t>)
+      user_launch(m, blocks, tensors, first);
+    else
+      user_launch(m, blocks, tensors);
+  };
   for (size_t i = 0; i < A.size(); ++i) {
     long n = A[i].numel();
     meta.a[t] = A[i].const_data_ptr();
@@ -375,6 +386,7 @@ static void mt_apply(const std::vector<at::Tensor>& A,
         meta.sizes[0] = meta.sizes[t];
         t = 0;
         blk = 0;
+        first = i;
       }
     }
     ++t;
@@ -382,6 +394,7 @@ static void mt_apply(const std::vector<at::Tensor>& A,
       if (blk) launch(meta, blk, t);
       t = 0;
       blk = 0;
+      first = i + 1;
     }
   }
   if (blk) launch(meta, blk, t);

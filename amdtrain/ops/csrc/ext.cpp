@@ -11,6 +11,16 @@ void multi_tensor_sgd(std::vector<at::Tensor> params,
                       double momentum, double weight_decay, bool nesterov,
                       bool first, bool zero_grad);
 
+// lars.hip (returns the per-tensor trust ratios)
+at::Tensor multi_tensor_lars(std::vector<at::Tensor> params,
+                             std::vector<at::Tensor> grads,
+                             std::vector<at::Tensor> momenta,
+                             std::vector<bool> adapt_mask,
+                             std::vector<bool> decay_mask, double lr,
+                             double momentum, double weight_decay, double eta,
+                             double eps, bool nesterov, bool first,
+                             bool zero_grad);
+
 // cross_entropy.hip
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor target);
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor target,
@@ -157,6 +167,7 @@ at::Tensor dwconv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "amdtrain hand-written gfx950 (CDNA4) HIP kernels";
   m.def("multi_tensor_sgd", &multi_tensor_sgd, "fused multi-tensor SGD");
+  m.def("multi_tensor_lars", &multi_tensor_lars, "fused multi-tensor LARS");
   m.def("cross_entropy_fwd", &cross_entropy_fwd);
   m.def("cross_entropy_bwd", &cross_entropy_bwd);
   m.def("normalize_u8", &normalize_u8);

@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         os.path.join(CSRC, "ext.cpp"),
         os.path.join(CSRC, "sgd.hip"),
+        os.path.join(CSRC, "lars.hip"),
         os.path.join(CSRC, "cross_entropy.hip"),
         os.path.join(CSRC, "elementwise.hip"),
         os.path.join(CSRC, "batchnorm.hip"),
