@@ -29,7 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import fused as OF
-from ..ops.conv import AmdConv2d, _pwconv_enabled, pw_thin_ok
+from ..ops.conv import (AmdConv2d, _pwconv_enabled, _pwwide_enabled,
+                        pw_thin_ok, pw_wide_ok)
 from ..ops.linear import AmdLinear
 from .resnet import FusedBatchNorm2d
 
@@ -45,26 +46,41 @@ _SETTINGS = [
 ]
 
 
+def _make_divisible(v: float, divisor: int) -> int:
+    """The nearest multiple of ``divisor`` (at least one), and the next one
+    up where that would lose more than a tenth of ``v``: the channel
+    rounding of the MobileNet family."""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    if new_v < 0.9 * v:
+        new_v += divisor
+    return new_v
+
+
 class LibraryConv2d(AmdConv2d):
     """An ``AmdConv2d`` that keeps off the MFMA GEMM: it runs on the thin
-    pointwise kernel when that is enabled and takes the layer, and on the
-    library (``nn.Conv2d``) path otherwise."""
+    pointwise kernel or on the pointwise GEMM of the 8 grid when the one
+    that takes the layer is enabled, and on the library (``nn.Conv2d``) path
+    otherwise."""
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if (_pwconv_enabled() and self.kernel_size == (1, 1)
-                and self.stride == (1, 1)
-                and pw_thin_ok(self.in_channels, self.out_channels)):
-            return AmdConv2d.forward(self, x)
+        if self.kernel_size == (1, 1) and self.stride == (1, 1):
+            pair = (self.in_channels, self.out_channels)
+            if ((_pwconv_enabled() and pw_thin_ok(*pair))
+                    or (_pwwide_enabled() and pw_wide_ok(*pair))):
+                return AmdConv2d.forward(self, x)
         return nn.Conv2d.forward(self, x)
 
 
 def _pointwise(inp: int, oup: int) -> AmdConv2d:
     """1x1 conv.  ``AmdConv2d`` sends in % 32 == 0, out % 32 == 0 to the
-    MFMA GEMM and the other widths of this model (``pw_thin_ok``) to the thin
-    pointwise kernel of ``ops/csrc/pwconv.hip``.  With that kernel switched
-    off (AMDTRAIN_PWCONV=0) in % 32 == 0, out % 16 == 0 goes to the GEMM,
+    MFMA GEMM, the thin widths off that grid (``pw_thin_ok``: all of them at
+    width 1.0) to the thin pointwise kernel of ``ops/csrc/pwconv.hip`` and
+    every other pair of multiples of 8 (``pw_wide_ok``: the other width
+    multipliers) to the pointwise GEMM of ``ops/csrc/pwgemm8.hip``.  With the
+    kernel that takes a layer switched off (AMDTRAIN_PWCONV=0,
+    AMDTRAIN_PWWIDE=0) in % 32 == 0, out % 16 == 0 goes to the MFMA GEMM,
     whose input gradient then needs out % 32 == 0 as its K and raises
-    otherwise; the one such layer here (32 -> 16, features.1) is a
+    otherwise; such a layer (32 -> 16, features.1, at width 1.0) is a
     ``LibraryConv2d``, which takes the library path in that case.
 
     The first two terms of the condition repeat ``ch_ok`` of
@@ -128,15 +144,21 @@ class InvertedResidual(nn.Module):
 
 
 class MobileNetV2(nn.Module):
-    def __init__(self, num_classes: int = 1000, dropout: float = 0.2):
+    """``width_mult`` scales every stage width, rounded to a multiple of
+    ``round_nearest`` (``_make_divisible``); the head only grows."""
+
+    def __init__(self, num_classes: int = 1000, dropout: float = 0.2,
+                 width_mult: float = 1.0, round_nearest: int = 8):
         super().__init__()
-        inp, last = 32, 1280
+        inp = _make_divisible(32 * width_mult, round_nearest)
+        last = _make_divisible(1280 * max(1.0, width_mult), round_nearest)
         features: List[nn.Module] = [ConvBNReLU6(3, inp, stride=2)]
         for t, c, n, s in _SETTINGS:
+            oup = _make_divisible(c * width_mult, round_nearest)
             for i in range(n):
                 features.append(
-                    InvertedResidual(inp, c, s if i == 0 else 1, t))
-                inp = c
+                    InvertedResidual(inp, oup, s if i == 0 else 1, t))
+                inp = oup
         features.append(ConvBNReLU6(inp, last, kernel_size=1))
         self.features = nn.Sequential(*features)
         self.classifier = nn.Sequential(
@@ -163,3 +185,15 @@ class MobileNetV2(nn.Module):
 
 def mobilenet_v2(num_classes: int = 1000, **kw) -> MobileNetV2:
     return MobileNetV2(num_classes=num_classes, **kw)
+
+
+def mobilenet_v2_050(num_classes: int = 1000, **kw) -> MobileNetV2:
+    return MobileNetV2(num_classes=num_classes, width_mult=0.5, **kw)
+
+
+def mobilenet_v2_075(num_classes: int = 1000, **kw) -> MobileNetV2:
+    return MobileNetV2(num_classes=num_classes, width_mult=0.75, **kw)
+
+
+def mobilenet_v2_140(num_classes: int = 1000, **kw) -> MobileNetV2:
+    return MobileNetV2(num_classes=num_classes, width_mult=1.4, **kw)

@@ -7,7 +7,8 @@ from typing import Callable, Dict, List
 
 import torch.nn as nn
 
-from .mobilenet import mobilenet_v2
+from .mobilenet import (mobilenet_v2, mobilenet_v2_050, mobilenet_v2_075,
+                        mobilenet_v2_140)
 from .resnet import (resnet18, resnet34, resnet50, resnet101, resnet152,
                      resnext50_32x4d, resnext101_32x8d, resnext101_64x4d,
                      wide_resnet50_2)
@@ -23,6 +24,9 @@ _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "resnext101_64x4d": resnext101_64x4d,
     "wide_resnet50_2": wide_resnet50_2,
     "mobilenet_v2": mobilenet_v2,
+    "mobilenet_v2_050": mobilenet_v2_050,
+    "mobilenet_v2_075": mobilenet_v2_075,
+    "mobilenet_v2_140": mobilenet_v2_140,
 }
 
 

@@ -6,7 +6,9 @@ pre-transposed weight.  Strided (downsample) 1x1 convs gather/scatter the
 even rows around the same GEMMs.  3x3, grouped 3x3 and the generic (stem)
 convs are implicit GEMMs over the same tiles.  Stride-1 1x1 convs with thin
 channel counts off the 32 grid (MobileNetV2's 16, 24, 144) run the same
-product on the skinny-GEMM kernel of pwconv.hip instead.
+product on the skinny-GEMM kernel of pwconv.hip instead, and every other
+pair of channel multiples of 8 off that grid (48, 88, 136, 224, 528, 816 of
+the width multipliers) on the tiled kernel of pwgemm8.hip.
 
 Every weight gradient is tn2_wgrad (wgrad.hip): one launch, split-M fp32
 partials collapsed in a fixed order, so it has no atomics and is bitwise
@@ -306,6 +308,74 @@ class _ConvPw(torch.autograd.Function):
 def conv1x1_thin(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """Stride-1 1x1 conv for channel counts inside ``pw_thin_ok``."""
     y, stats = _ConvPw.apply(x, weight)
+    if stats.numel():
+        y._amdtrain_bn_stats = stats
+    return y
+
+
+def _pwwide_enabled() -> bool:
+    """Pointwise MFMA GEMM on the 8 grid (pwgemm8.hip) for stride-1 1x1 convs
+    inside ``pw_wide_ok``; AMDTRAIN_PWWIDE=0 restores the routing from before
+    it (MFMA GEMM whose backward raises, generic kernel or MIOpen)."""
+    return os.environ.get("AMDTRAIN_PWWIDE", "1") == "1"
+
+
+def pw_wide_ok(cin: int, cout: int) -> bool:
+    """True when a stride-1, pad-0, ungrouped, bias-free 1x1 conv
+    cin -> cout belongs to the pointwise GEMM on the 8 grid: both counts
+    multiples of 8, not on the MFMA GEMM's 32 grid and not the thin kernel's
+    (``pw_thin_ok``).  Symmetric in (cin, cout), as the input gradient is the
+    same product with K and N swapped.  Pure Python; needs no GPU."""
+    if cin < 8 or cout < 8 or cin % 8 or cout % 8:
+        return False
+    if cin % 32 == 0 and cout % 32 == 0:
+        return False
+    return not pw_thin_ok(cin, cout)
+
+
+class _ConvPwWide(torch.autograd.Function):
+    """Stride-1 1x1 conv with channel counts on the 8 grid over pw8_gemm
+    (pwgemm8.hip): forward with the BN-statistics partials as a second,
+    non-differentiable output, input gradient as the same kernel on the
+    transposed weight, weight gradient as tn2_wgrad."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        e = require_ext()
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        xc = x.contiguous(memory_format=torch.channels_last)
+        x2d = _rows(xc)
+        w2d = weight.reshape(cout, cin)
+        y2d, stats = e.pw8_gemm(x2d, w2d, _fuse_stats_enabled())
+        ctx.save_for_backward(x2d, w2d)
+        ctx.meta = (n, cin, h, w, cout)
+        y = y2d.view(n, h, w, cout).permute(0, 3, 1, 2)
+        ctx.mark_non_differentiable(stats)
+        return y, stats
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor, _grad_stats=None):
+        e = require_ext()
+        x2d, w2d = ctx.saved_tensors
+        n, cin, h, w, cout = ctx.meta
+        gy = grad_y.contiguous(memory_format=torch.channels_last)
+        gy2d = _rows(gy).to(torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wT = e.transpose_2d(w2d)                  # [Cin, Cout]
+            dx2d = e.pw8_gemm(gy2d, wT, False)[0]     # [R, Cin] bf16
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = e.tn2_wgrad(gy2d, x2d).reshape(cout, cin, 1, 1)
+        return dx, dw
+
+
+def conv1x1_wide(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """Stride-1 1x1 conv for channel counts inside ``pw_wide_ok``."""
+    y, stats = _ConvPwWide.apply(x, weight)
     if stats.numel():
         y._amdtrain_bn_stats = stats
     return y
@@ -768,6 +838,9 @@ class AmdConv2d(nn.Conv2d):
     1x1 -> MFMA GEMM (gemm.hip), or, stride 1 with channel counts off the
     32 grid but inside ``pw_thin_ok``, the thin pointwise kernel
     (pwconv.hip; AMDTRAIN_PWCONV=0 restores the routing from before it),
+    or, for every other pair of channel multiples of 8 off that grid
+    (``pw_wide_ok``), the pointwise GEMM on the 8 grid (pwgemm8.hip;
+    AMDTRAIN_PWWIDE=0 likewise),
     3x3 pad-1 s1/s2 -> implicit GEMM
     (conv3x3.hip), anything else without an input gradient (the 7x7
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
@@ -829,6 +902,14 @@ class AmdConv2d(nn.Conv2d):
                     and _pwconv_enabled()
                     and _conv1x1_env_default() == "custom"):
                 return conv1x1_thin(x, self.weight)
+            # every other stride-1 1x1 on the 8 grid but off the 32 grid:
+            # before ch_ok, whose backward needs out % 32 == 0
+            if (self.kernel_size == (1, 1) and self.padding == (0, 0)
+                    and self.stride == (1, 1)
+                    and pw_wide_ok(self.in_channels, self.out_channels)
+                    and _pwwide_enabled()
+                    and _conv1x1_env_default() == "custom"):
+                return conv1x1_wide(x, self.weight)
             if (ch_ok and self.kernel_size == (1, 1)
                     and self.padding == (0, 0)
                     and _conv1x1_env_default() == "custom"):

@@ -35,6 +35,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "dwconv.hip"),
         os.path.join(CSRC, "pwconv.hip"),
+        os.path.join(CSRC, "pwgemm8.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
