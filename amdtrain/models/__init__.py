@@ -13,6 +13,7 @@ from .resnet import (
     wide_resnet50_2,
 )
 from .mobilenet import MobileNetV2, InvertedResidual, mobilenet_v2
+from .mnasnet import MNASNet, mnasnet0_5, mnasnet1_0
 from .registry import build_model, model_names
 
 __all__ = [
@@ -21,4 +22,5 @@ __all__ = [
     "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d",
     "wide_resnet50_2",
     "MobileNetV2", "InvertedResidual", "mobilenet_v2",
+    "MNASNet", "mnasnet0_5", "mnasnet1_0",
 ]

@@ -7,6 +7,7 @@ from typing import Callable, Dict, List
 
 import torch.nn as nn
 
+from .mnasnet import mnasnet0_5, mnasnet1_0
 from .mobilenet import (mobilenet_v2, mobilenet_v2_050, mobilenet_v2_075,
                         mobilenet_v2_140)
 from .resnet import (resnet18, resnet34, resnet50, resnet101, resnet152,
@@ -27,6 +28,8 @@ _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "mobilenet_v2_050": mobilenet_v2_050,
     "mobilenet_v2_075": mobilenet_v2_075,
     "mobilenet_v2_140": mobilenet_v2_140,
+    "mnasnet0_5": mnasnet0_5,
+    "mnasnet1_0": mnasnet1_0,
 }
 
 

@@ -673,6 +673,61 @@ def dwconv3x3(x: torch.Tensor, weight: torch.Tensor,
                                       x.shape[1])
 
 
+class _DwConv5x5(torch.autograd.Function):
+    """Depthwise 5x5 pad-2 conv (stride 1/2) over the LDS halo-tile kernels
+    of dwconv5x5.hip: forward, input gradient (the forward kernel with
+    mirrored taps at stride 1, a parity gather at stride 2) and a two-level
+    fixed-order weight gradient, all NHWC bf16 with fp32 accumulation.  The
+    kernels take the weight tap-major, ``w25`` [25, C]."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+        e = require_ext()
+        n, c, h, w = x.shape
+        xc = x.to(torch.bfloat16) \
+            .contiguous(memory_format=torch.channels_last)
+        x2d = _rows(xc)
+        wb = weight.to(torch.bfloat16)
+        w25 = wb.reshape(c, 25).t().contiguous()
+        y2d = e.dwconv5x5_fwd(x2d, n, h, w, stride, w25)
+        ctx.save_for_backward(x2d, wb)
+        ctx.meta = (n, c, h, w, stride)
+        ho = (h + 4 - 5) // stride + 1
+        wo = (w + 4 - 5) // stride + 1
+        return y2d.view(n, ho, wo, c).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor):
+        e = require_ext()
+        x2d, wb = ctx.saved_tensors
+        n, c, h, w, stride = ctx.meta
+        gy = grad_y.contiguous(memory_format=torch.channels_last)
+        gy2d = _rows(gy).to(torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            w25 = wb.reshape(c, 25).t().contiguous()
+            dx2d = e.dwconv5x5_dgrad(gy2d, n, h, w, stride, w25)
+            dx = dx2d.view(n, h, w, c).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw25 = e.dwconv5x5_wgrad(gy2d, x2d, n, h, w, stride)  # [25, C]
+            dw = dw25.t().reshape(c, 1, 5, 5)
+        return dx, dw, None
+
+
+def dwconv5x5(x: torch.Tensor, weight: torch.Tensor,
+              stride: int = 1) -> torch.Tensor:
+    """Depthwise 5x5 pad-2 conv, ``weight`` [C, 1, 5, 5], stride 1 or 2.
+    On the GPU with the extension loaded: the bf16 halo-tile kernels (C must
+    be a multiple of 8).  On CPU, or with the extension off: exactly
+    ``F.conv2d(..., groups=C)``."""
+    if x.is_cuda and ext_available():
+        return _DwConv5x5.apply(x, weight, stride)
+    return torch.nn.functional.conv2d(x, weight, None, stride, 2, 1,
+                                      x.shape[1])
+
+
 def stem_s2d_input(x_nhwc: torch.Tensor) -> torch.Tensor:
     """[N, H, W, C] (C <= 4, W even) -> X' [N, H, W/2, 8]: channels padded
     to 4, then two neighbouring pixels share one 8-channel row, channel
@@ -845,7 +900,10 @@ class AmdConv2d(nn.Conv2d):
     (conv3x3.hip), anything else without an input gradient (the 7x7
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
     Depthwise 3x3 pad-1 s1/s2 (groups == in == out channels, C % 8 == 0)
-    -> vectorised stencil (dwconv.hip); other grouped 3x3 with
+    -> vectorised stencil (dwconv.hip); depthwise 5x5 pad-2 s1/s2 under the
+    same conditions -> LDS halo-tile kernels (dwconv5x5.hip;
+    AMDTRAIN_DWCONV5X5=0 sends only these to the library,
+    AMDTRAIN_DWCONV=miopen both sizes); other grouped 3x3 with
     in % 32 == 0 and out % 16 == 0 (ResNeXt) -> the per-group MFMA kernel
     (gconv.hip) when in == out and in / groups is 4, 8, 16 or 32
     (AMDTRAIN_GCONV=0 switches it off), else the block-diagonalized dense
@@ -873,6 +931,16 @@ class AmdConv2d(nn.Conv2d):
                 if os.environ.get("AMDTRAIN_DWCONV", "custom") == "miopen":
                     return super().forward(x)
                 return dwconv3x3(x, self.weight, self.stride[0])
+            # depthwise 5x5: LDS halo tiles
+            if (self.groups == self.in_channels == self.out_channels
+                    and self.kernel_size == (5, 5)
+                    and self.padding == (2, 2)
+                    and self.stride in ((1, 1), (2, 2))
+                    and self.in_channels % 8 == 0):
+                if (os.environ.get("AMDTRAIN_DWCONV", "custom") == "miopen"
+                        or os.environ.get("AMDTRAIN_DWCONV5X5", "1") == "0"):
+                    return super().forward(x)
+                return dwconv5x5(x, self.weight, self.stride[0])
             # grouped 3x3 (ResNeXt): per-group kernel inside its contract,
             # block-diagonalized dense path otherwise
             if (self.kernel_size == (3, 3) and self.padding == (1, 1)

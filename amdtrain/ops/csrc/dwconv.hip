@@ -22,39 +22,9 @@
 // output rows into fp32 partials [P, 9, C], a second kernel collapses the
 // partials in a fixed order.  P is a function of the shape alone, so the
 // result is bitwise reproducible.  No atomics anywhere.
-#include "common.h"
+#include "dwconv_common.h"
 
 namespace {
-
-constexpr int DW_TW = 4;      // columns per lane strip
-constexpr int DW_L2E = 32;    // elements per block of the wgrad collapse
-constexpr int DW_L2G = 8;     // ... and partial groups per element
-
-using bf16 = __hip_bfloat16;
-using Pk8 = Pack<bf16, 8>;
-
-__device__ __forceinline__ void load8(const bf16* p, float f[8]) {
-  Pk8 v = *reinterpret_cast<const Pk8*>(p);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) f[j] = to_f32<bf16>(v.v[j]);
-}
-
-__device__ __forceinline__ void load8_pred(const bf16* p, bool ok,
-                                           float f[8]) {
-  if (ok) {
-    load8(p, f);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = 0.f;
-  }
-}
-
-__device__ __forceinline__ void store8(bf16* p, const float f[8]) {
-  Pk8 v;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v.v[j] = from_f32<bf16>(f[j]);
-  *reinterpret_cast<Pk8*>(p) = v;
-}
 
 // y(ho, wo) = sum_{kh,kw} x(ho*S - 1 + kh, wo*S - 1 + kw) * w[kh][kw].
 // MIRROR reads tap (2-kh, 2-kw) instead: with x = dy and S = 1 that is the
@@ -267,70 +237,14 @@ __global__ __launch_bounds__(AMD_TPB) void dwconv3x3_wgrad_part_kernel(
   }
 }
 
-// Weight gradient, level 2: out[e] = sum_p part[p][e], e over 9*C.  A block
-// takes DW_L2E elements; each of its DW_L2G thread groups sums the partials
-// p = g, g + DW_L2G, ... in order (four loads in flight, added in p order;
-// a slot past P adds 0.f, which changes nothing), then the groups are added
-// in group order.
-__global__ __launch_bounds__(AMD_TPB) void dwconv3x3_wgrad_collapse_kernel(
-    const float* __restrict__ part, float* __restrict__ out, int P, int E) {
-  static_assert(AMD_TPB == DW_L2E * DW_L2G, "elements x groups");
-  __shared__ float red[AMD_TPB];
-  const int lane = threadIdx.x % DW_L2E;
-  const int g = threadIdx.x / DW_L2E;
-  const int e = blockIdx.x * DW_L2E + lane;
-  float s = 0.f;
-  if (e < E) {
-    for (int p = g; p < P; p += 4 * DW_L2G) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pu = p + u * DW_L2G;
-        v[u] = pu < P ? part[(long)pu * E + e] : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += v[u];
-    }
-  }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (g == 0 && e < E) {
-    float tot = red[lane];
-#pragma unroll
-    for (int k = 1; k < DW_L2G; ++k) tot += red[k * DW_L2E + lane];
-    out[e] = tot;
-  }
-}
-
-struct DwGeom {
-  long C, CP, Ho, Wo;
-};
-
-// Shared host-side contract of the three entry points.
 DwGeom dw_check(const at::Tensor& a2d, const char* what, long Nn, long H,
                 long W, long stride, long rows_h, long rows_w) {
-  TORCH_CHECK(a2d.is_cuda() && a2d.scalar_type() == at::kBFloat16 &&
-                  a2d.dim() == 2 && a2d.is_contiguous(),
-              what, " must be a contiguous 2-D bf16 GPU tensor");
-  TORCH_CHECK(stride == 1 || stride == 2, "dwconv3x3: stride must be 1 or 2");
-  TORCH_CHECK(Nn >= 0 && H >= 1 && W >= 1, "dwconv3x3: bad geometry");
-  TORCH_CHECK(H < (1 << 24) && W < (1 << 24), "dwconv3x3: image too large");
-  const long C = a2d.size(1);
-  TORCH_CHECK(C >= 8 && C % 8 == 0,
-              "dwconv3x3: C must be a positive multiple of 8, got ", C);
-  TORCH_CHECK(C < (1 << 24), "dwconv3x3: C too large");
-  const long Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-  const long eh = rows_h ? Ho : H, ew = rows_w ? Wo : W;
-  TORCH_CHECK(a2d.size(0) == Nn * eh * ew, what, " has ", a2d.size(0),
-              " rows, geometry needs ", Nn * eh * ew);
-  return {C, C / 8, Ho, Wo};
+  return dw_check("dwconv3x3", 3, a2d, what, Nn, H, W, stride, rows_h,
+                  rows_w);
 }
 
 void dw_check_w9(const at::Tensor& w9, const at::Tensor& like, long C) {
-  TORCH_CHECK(w9.is_cuda() && w9.scalar_type() == at::kBFloat16 &&
-                  w9.dim() == 2 && w9.is_contiguous() && w9.size(0) == 9 &&
-                  w9.size(1) == C && w9.device() == like.device(),
-              "w9 must be a contiguous [9, C] bf16 tensor on the same GPU");
+  dw_check_w("w9", 9, w9, like, C);
 }
 
 long dw_blocks(long total) {
@@ -431,10 +345,6 @@ at::Tensor dwconv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
         (int)g.C, (int)g.CP, (int)CPB, (int)nslots, (int)nstrips, (int)RC,
         NR);
   CHECK_CUDA_OK();
-  const long E = 9 * g.C;
-  dwconv3x3_wgrad_collapse_kernel<<<(unsigned)((E + DW_L2E - 1) / DW_L2E), AMD_TPB, 0,
-                                    stream>>>(
-      part.data_ptr<float>(), dw9.data_ptr<float>(), (int)P, (int)E);
-  CHECK_CUDA_OK();
+  dw_collapse(part, dw9, P, 9 * g.C, stream);
   return dw9;
 }

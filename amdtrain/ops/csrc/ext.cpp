@@ -166,6 +166,14 @@ at::Tensor dwconv3x3_dgrad(at::Tensor dy2d, long Nn, long H, long W,
 at::Tensor dwconv3x3_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
                            long W, long stride);
 
+// dwconv5x5.hip
+at::Tensor dwconv5x5_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
+                         at::Tensor w25);
+at::Tensor dwconv5x5_dgrad(at::Tensor dy2d, long Nn, long H, long W,
+                           long stride, at::Tensor w25);
+at::Tensor dwconv5x5_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
+                           long W, long stride);
+
 // epi (trailing, defaulted): AMDTRAIN_EPILOGUE mode of the bf16 C store,
 // 0 / 1 / 2 (csrc/common.h); -1 = each kernel's measured default
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -279,6 +287,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv3x3_dgrad", &dwconv3x3_dgrad, py::arg("dy2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w9"));
   m.def("dwconv3x3_wgrad", &dwconv3x3_wgrad, py::arg("dy2d"),
+        py::arg("x2d"), py::arg("Nn"), py::arg("H"), py::arg("W"),
+        py::arg("stride"));
+  m.def("dwconv5x5_fwd", &dwconv5x5_fwd, py::arg("x2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w25"));
+  m.def("dwconv5x5_dgrad", &dwconv5x5_dgrad, py::arg("dy2d"), py::arg("Nn"),
+        py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w25"));
+  m.def("dwconv5x5_wgrad", &dwconv5x5_wgrad, py::arg("dy2d"),
         py::arg("x2d"), py::arg("Nn"), py::arg("H"), py::arg("W"),
         py::arg("stride"));
 }

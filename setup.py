@@ -34,6 +34,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "wgrad.hip"),
         os.path.join(CSRC, "pool.hip"),
         os.path.join(CSRC, "dwconv.hip"),
+        os.path.join(CSRC, "dwconv5x5.hip"),
         os.path.join(CSRC, "pwconv.hip"),
         os.path.join(CSRC, "pwgemm8.hip"),
     ],

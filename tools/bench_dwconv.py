@@ -1,8 +1,10 @@
 """Depthwise 3x3: the stencil kernels (dwconv.hip) against the library path
 that AMDTRAIN_DWCONV=miopen takes, on the ten MobileNetV2 depthwise shapes
-at 224 input.
+at 224 input.  With K = 5: the halo-tile kernels (dwconv5x5.hip) on the six
+depthwise 5x5 shapes of mnasnet1_0 (AMDTRAIN_DWCONV=miopen and
+AMDTRAIN_DWCONV5X5=0 send a 5x5 layer down the same library path).
 
-    python tools/bench_dwconv.py [BATCH]        (default 256)
+    python tools/bench_dwconv.py [BATCH] [K]    (default 256, 3)
 
 Both sides run through the same ``AmdConv2d`` layer under bf16 autocast; the
 environment switch alone decides the path, and the library is set up as in
@@ -12,7 +14,7 @@ the layer call; dgrad and wgrad are ``torch.autograd.grad`` of kept graphs in
 which only the input, or only the weight, requires a gradient, so each is
 one kernel family (plus, on both sides alike, the layout/cast glue around
 it; the custom wgrad figure includes building dw [C,1,3,3] from the
-kernel's [9,C]).
+kernel's [K*K,C]).
 A last column times the custom kernels alone through ``_C``: at the small
 late-stage shapes the layer route is bound by Python, not by the GPU.
 
@@ -33,6 +35,9 @@ from amdtrain.ops.conv import AmdConv2d  # noqa: E402
 SHAPES = [(32, 1, 112), (96, 2, 112), (144, 1, 56), (144, 2, 56),
           (192, 1, 28), (192, 2, 28), (384, 1, 14), (576, 1, 14),
           (576, 2, 14), (960, 1, 7)]
+# ... and of the depthwise 5x5 layers of mnasnet1_0
+SHAPES5 = [(72, 2, 56), (120, 1, 28), (240, 2, 28), (480, 1, 14),
+           (576, 2, 14), (1152, 1, 7)]
 
 
 def time_fn(fn, iters=20):
@@ -83,17 +88,17 @@ class Side:
                                    retain_graph=True)[0]
 
 
-def run(n, c, stride, hw):
+def run(n, c, stride, hw, k=3):
     torch.manual_seed(0)
-    ho = (hw + 2 - 3) // stride + 1
+    ho = (hw - 1) // stride + 1
     x = torch.randn(n, c, hw, hw, device="cuda").bfloat16() \
         .contiguous(memory_format=torch.channels_last)
     gy = torch.randn(n, c, ho, ho, device="cuda").bfloat16() \
         .contiguous(memory_format=torch.channels_last)
-    conv = AmdConv2d(c, c, 3, stride=stride, padding=1, groups=c,
+    conv = AmdConv2d(c, c, k, stride=stride, padding=k // 2, groups=c,
                      bias=False).cuda().to(memory_format=torch.channels_last)
     with torch.no_grad():
-        conv.weight.copy_((torch.randn(c, 1, 3, 3, device="cuda") / 3)
+        conv.weight.copy_((torch.randn(c, 1, k, k, device="cuda") / k)
                           .bfloat16())
     custom = Side("custom", conv, x, gy)
     lib = Side("miopen", conv, x, gy)
@@ -108,12 +113,19 @@ def run(n, c, stride, hw):
     # the bare kernels, without the autograd and layout glue of the layer
     x2d = x.permute(0, 2, 3, 1).reshape(-1, c)
     gy2d = gy.permute(0, 2, 3, 1).reshape(-1, c)
-    w9 = conv.weight.detach().bfloat16().reshape(c, 9).t().contiguous()
-    kernel = {
-        "fwd": lambda: _C.dwconv3x3_fwd(x2d, n, hw, hw, stride, w9),
-        "dgrad": lambda: _C.dwconv3x3_dgrad(gy2d, n, hw, hw, stride, w9),
-        "wgrad": lambda: _C.dwconv3x3_wgrad(gy2d, x2d, n, hw, hw, stride),
-    }
+    wk = conv.weight.detach().bfloat16().reshape(c, k * k).t().contiguous()
+    if k == 3:
+        kernel = {
+            "fwd": lambda: _C.dwconv3x3_fwd(x2d, n, hw, hw, stride, wk),
+            "dgrad": lambda: _C.dwconv3x3_dgrad(gy2d, n, hw, hw, stride, wk),
+            "wgrad": lambda: _C.dwconv3x3_wgrad(gy2d, x2d, n, hw, hw, stride),
+        }
+    else:
+        kernel = {
+            "fwd": lambda: _C.dwconv5x5_fwd(x2d, n, hw, hw, stride, wk),
+            "dgrad": lambda: _C.dwconv5x5_dgrad(gy2d, n, hw, hw, stride, wk),
+            "wgrad": lambda: _C.dwconv5x5_wgrad(gy2d, x2d, n, hw, hw, stride),
+        }
     nbytes = 2.0 * (x.numel() + gy.numel())   # the same for all three passes
     for name in ("fwd", "dgrad", "wgrad"):
         tc = best(getattr(custom, name))
@@ -128,6 +140,8 @@ def run(n, c, stride, hw):
 if __name__ == "__main__":
     torch.backends.cudnn.benchmark = True
     batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-    for c, stride, hw in SHAPES:
-        run(batch, c, stride, hw)
+    ksize = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    assert ksize in (3, 5)
+    for c, stride, hw in (SHAPES if ksize == 3 else SHAPES5):
+        run(batch, c, stride, hw, ksize)
     os.environ.pop("AMDTRAIN_DWCONV", None)
