@@ -14,6 +14,7 @@ from .resnet import (
 )
 from .mobilenet import MobileNetV2, InvertedResidual, mobilenet_v2
 from .mnasnet import MNASNet, mnasnet0_5, mnasnet1_0
+from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small
 from .registry import build_model, model_names
 
 __all__ = [
@@ -23,4 +24,5 @@ __all__ = [
     "wide_resnet50_2",
     "MobileNetV2", "InvertedResidual", "mobilenet_v2",
     "MNASNet", "mnasnet0_5", "mnasnet1_0",
+    "MobileNetV3", "mobilenet_v3_large", "mobilenet_v3_small",
 ]

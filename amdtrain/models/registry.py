@@ -10,6 +10,7 @@ import torch.nn as nn
 from .mnasnet import mnasnet0_5, mnasnet1_0
 from .mobilenet import (mobilenet_v2, mobilenet_v2_050, mobilenet_v2_075,
                         mobilenet_v2_140)
+from .mobilenetv3 import mobilenet_v3_large, mobilenet_v3_small
 from .resnet import (resnet18, resnet34, resnet50, resnet101, resnet152,
                      resnext50_32x4d, resnext101_32x8d, resnext101_64x4d,
                      wide_resnet50_2)
@@ -28,6 +29,8 @@ _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "mobilenet_v2_050": mobilenet_v2_050,
     "mobilenet_v2_075": mobilenet_v2_075,
     "mobilenet_v2_140": mobilenet_v2_140,
+    "mobilenet_v3_large": mobilenet_v3_large,
+    "mobilenet_v3_small": mobilenet_v3_small,
     "mnasnet0_5": mnasnet0_5,
     "mnasnet1_0": mnasnet1_0,
 }

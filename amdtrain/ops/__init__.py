@@ -15,6 +15,7 @@ from . import fused  # noqa: F401
 from .sgd import FusedSGD  # noqa: F401
 from .lars import FusedLARS  # noqa: F401
 from .cross_entropy import CrossEntropyLoss  # noqa: F401
+from .se import SqueezeExcite, hardswish, squeeze_excite  # noqa: F401
 
 __all__ = ["functional", "fused", "FusedSGD", "FusedLARS",
-           "CrossEntropyLoss"]
+           "CrossEntropyLoss", "SqueezeExcite", "hardswish", "squeeze_excite"]

@@ -174,6 +174,25 @@ at::Tensor dwconv5x5_dgrad(at::Tensor dy2d, long Nn, long H, long W,
 at::Tensor dwconv5x5_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
                            long W, long stride);
 
+// se.hip
+at::Tensor se_squeeze(at::Tensor x2d, long N, long HW, bool hswish,
+                      long splits);
+std::vector<at::Tensor> se_excite(at::Tensor part, long HW, at::Tensor w1,
+                                  at::Tensor b1, at::Tensor w2, at::Tensor b2);
+at::Tensor se_scale(at::Tensor x2d, at::Tensor s, long N, long HW,
+                    bool hswish);
+at::Tensor se_bwd_reduce(at::Tensor dy2d, at::Tensor x2d, long N, long HW,
+                         bool hswish, long splits);
+std::vector<at::Tensor> se_excite_bwd(at::Tensor ds_part, at::Tensor s,
+                                      at::Tensor h, at::Tensor w1,
+                                      at::Tensor w2, long HW);
+std::vector<at::Tensor> se_wgrad(at::Tensor dz2, at::Tensor dz1,
+                                 at::Tensor mean, at::Tensor h);
+at::Tensor se_bwd_apply(at::Tensor dy2d, at::Tensor x2d, at::Tensor s,
+                        at::Tensor dm, long N, long HW, bool hswish);
+at::Tensor hardswish_fwd(at::Tensor x);
+at::Tensor hardswish_bwd(at::Tensor grad_y, at::Tensor x);
+
 // epi (trailing, defaulted): AMDTRAIN_EPILOGUE mode of the bf16 C store,
 // 0 / 1 / 2 (csrc/common.h); -1 = each kernel's measured default
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -296,4 +315,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dwconv5x5_wgrad", &dwconv5x5_wgrad, py::arg("dy2d"),
         py::arg("x2d"), py::arg("Nn"), py::arg("H"), py::arg("W"),
         py::arg("stride"));
+  m.def("se_squeeze", &se_squeeze, py::arg("x2d"), py::arg("N"),
+        py::arg("HW"), py::arg("hswish"), py::arg("splits") = 0);
+  m.def("se_excite", &se_excite, py::arg("part"), py::arg("HW"),
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"));
+  m.def("se_scale", &se_scale, py::arg("x2d"), py::arg("s"), py::arg("N"),
+        py::arg("HW"), py::arg("hswish"));
+  m.def("se_bwd_reduce", &se_bwd_reduce, py::arg("dy2d"), py::arg("x2d"),
+        py::arg("N"), py::arg("HW"), py::arg("hswish"),
+        py::arg("splits") = 0);
+  m.def("se_excite_bwd", &se_excite_bwd, py::arg("ds_part"), py::arg("s"),
+        py::arg("h"), py::arg("w1"), py::arg("w2"), py::arg("HW"));
+  m.def("se_wgrad", &se_wgrad, py::arg("dz2"), py::arg("dz1"),
+        py::arg("mean"), py::arg("h"));
+  m.def("se_bwd_apply", &se_bwd_apply, py::arg("dy2d"), py::arg("x2d"),
+        py::arg("s"), py::arg("dm"), py::arg("N"), py::arg("HW"),
+        py::arg("hswish"));
+  m.def("hardswish_fwd", &hardswish_fwd);
+  m.def("hardswish_bwd", &hardswish_bwd);
 }

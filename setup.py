@@ -37,6 +37,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "dwconv5x5.hip"),
         os.path.join(CSRC, "pwconv.hip"),
         os.path.join(CSRC, "pwgemm8.hip"),
+        os.path.join(CSRC, "se.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
