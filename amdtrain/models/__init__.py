@@ -15,6 +15,7 @@ from .resnet import (
 from .mobilenet import MobileNetV2, InvertedResidual, mobilenet_v2
 from .mnasnet import MNASNet, mnasnet0_5, mnasnet1_0
 from .mobilenetv3 import MobileNetV3, mobilenet_v3_large, mobilenet_v3_small
+from .efficientnet import EfficientNet, MBConv, efficientnet_b0
 from .registry import build_model, model_names
 
 __all__ = [
@@ -25,4 +26,5 @@ __all__ = [
     "MobileNetV2", "InvertedResidual", "mobilenet_v2",
     "MNASNet", "mnasnet0_5", "mnasnet1_0",
     "MobileNetV3", "mobilenet_v3_large", "mobilenet_v3_small",
+    "EfficientNet", "MBConv", "efficientnet_b0",
 ]

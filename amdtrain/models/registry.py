@@ -7,6 +7,7 @@ from typing import Callable, Dict, List
 
 import torch.nn as nn
 
+from .efficientnet import efficientnet_b0
 from .mnasnet import mnasnet0_5, mnasnet1_0
 from .mobilenet import (mobilenet_v2, mobilenet_v2_050, mobilenet_v2_075,
                         mobilenet_v2_140)
@@ -33,6 +34,7 @@ _REGISTRY: Dict[str, Callable[..., nn.Module]] = {
     "mobilenet_v3_small": mobilenet_v3_small,
     "mnasnet0_5": mnasnet0_5,
     "mnasnet1_0": mnasnet1_0,
+    "efficientnet_b0": efficientnet_b0,
 }
 
 

@@ -18,8 +18,8 @@
 // All ResNet channel counts (64..2048) hit this register path.
 //
 // These kernels take power-of-two C only.  Any other C with whole 16-byte
-// packs and at most 256 of them per row, and every ReLU6, runs on the
-// kernels of batchnorm_anyc.h, behind the same entries and the same
+// packs and at most 256 of them per row, and every ReLU6 and SiLU, runs on
+// the kernels of batchnorm_anyc.h, behind the same entries and the same
 // collapse / finalize stages.
 #include <cstdlib>
 #include <cstring>
@@ -871,16 +871,19 @@ static void dispatch_vec(const at::Tensor& x, F fn) {
 
 static bool bn_pow2(long C) { return (C & (C - 1)) == 0; }
 
-// the forward / backward activation selector of the entries' two flags
-static int bn_act(bool relu, bool relu6) {
+// the forward / backward activation selector of the entries' three flags
+static int bn_act(bool relu, bool relu6, bool silu) {
   TORCH_CHECK(!(relu && relu6), "batch_norm: relu and relu6 are exclusive");
-  return relu6 ? BN_ACT_RELU6 : relu ? BN_ACT_RELU : BN_ACT_NONE;
+  TORCH_CHECK(!(silu && (relu || relu6)),
+              "batch_norm: silu excludes relu and relu6");
+  return silu ? BN_ACT_SILU
+              : relu6 ? BN_ACT_RELU6 : relu ? BN_ACT_RELU : BN_ACT_NONE;
 }
 
 // which family serves (C, act): the power-of-two kernels keep every shape
-// they served before ReLU6 existed
+// they served before ReLU6 existed; every ReLU6 and every SiLU is any-C
 static bool bn_use_anyc(long C, int act) {
-  return !bn_pow2(C) || act == BN_ACT_RELU6;
+  return !bn_pow2(C) || act == BN_ACT_RELU6 || act == BN_ACT_SILU;
 }
 
 // the any-C contract: whole 16-byte packs, one channel group per thread
@@ -900,7 +903,8 @@ static void bn_check_fwd_form(const at::Tensor& x, int act,
   if (!bn_use_anyc(C, act)) return;
   bn_check_anyc_channels(x);
   TORCH_CHECK(!(addend && act != BN_ACT_NONE), "batch_norm: an addend under ",
-              act == BN_ACT_RELU6 ? "ReLU6" : "ReLU",
+              act == BN_ACT_SILU ? "SiLU"
+                                 : act == BN_ACT_RELU6 ? "ReLU6" : "ReLU",
               " is not built for this channel count: C = ", C);
 }
 
@@ -953,6 +957,7 @@ static void bn_apply_launch(const at::Tensor& x,
       (const devT*)x.const_data_ptr(), zp, (devT*)y.data_ptr(),             \
       scale.data_ptr<float>(), shift.data_ptr<float>(), total_vec, (int)C)
       if (addend) APPLY_ANYC(BN_ACT_NONE, true);
+      else if (act == BN_ACT_SILU) APPLY_ANYC(BN_ACT_SILU, false);
       else if (act == BN_ACT_RELU6) APPLY_ANYC(BN_ACT_RELU6, false);
       else if (act == BN_ACT_RELU) APPLY_ANYC(BN_ACT_RELU, false);
       else APPLY_ANYC(BN_ACT_NONE, false);
@@ -1199,9 +1204,9 @@ std::vector<at::Tensor> batch_norm_train_stats(
 std::vector<at::Tensor> batch_norm_fwd_train(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
     at::Tensor running_var, double momentum, double eps, bool relu,
-    std::optional<at::Tensor> addend, bool relu6) {
+    std::optional<at::Tensor> addend, bool relu6, bool silu) {
   check_nhwc(x);
-  const int act = bn_act(relu, relu6);
+  const int act = bn_act(relu, relu6, silu);
   bn_check_fwd_form(x, act, addend);
   const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const long R = N * H * W;
@@ -1226,9 +1231,10 @@ std::vector<at::Tensor> batch_norm_fwd_train(
 std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
     at::Tensor x, at::Tensor parts, at::Tensor weight, at::Tensor bias,
     at::Tensor running_mean, at::Tensor running_var, double momentum,
-    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6) {
+    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6,
+    bool silu) {
   check_nhwc(x);
-  const int act = bn_act(relu, relu6);
+  const int act = bn_act(relu, relu6, silu);
   bn_check_fwd_form(x, act, addend);
   const long C = x.size(1);
   const long R = x.numel() / C;
@@ -1349,9 +1355,10 @@ std::vector<at::Tensor> batch_norm_dual_bwd(
 at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
-                               std::optional<at::Tensor> addend, bool relu6) {
+                               std::optional<at::Tensor> addend, bool relu6,
+                               bool silu) {
   check_nhwc(x);
-  const int act = bn_act(relu, relu6);
+  const int act = bn_act(relu, relu6, silu);
   bn_check_fwd_form(x, act, addend);
   const long C = x.size(1);
   const long R = x.numel() / C;
@@ -1380,8 +1387,10 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
                                        std::optional<at::Tensor> relu_mask,
-                                       bool grad_out2_compact, bool relu6) {
-  // relu6, or a C that is not a power of two: the any-C kernels (below).
+                                       bool grad_out2_compact, bool relu6,
+                                       bool silu) {
+  // relu6, silu, or a C that is not a power of two: the any-C kernels
+  // (below).
   // grad_out2_compact: grad_out2 is the [N*Hs*Ws, C] dgrad of a stride-2
   // 1x1 conv (Hs = ceil(H/2), Ws = ceil(W/2)); the reduce reads it at the
   // even positions and adds 0 elsewhere, which is the tensor
@@ -1398,7 +1407,7 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
   //                            disappears entirely (2 passes saved)
   check_nhwc(x);
   check_nhwc(grad_out);
-  const int act = bn_act(relu, relu6);
+  const int act = bn_act(relu, relu6, silu);
   const long C = x.size(1);
   const long R = x.numel() / C;
   auto opts = x.options().dtype(at::kFloat);
@@ -1411,7 +1420,8 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                     grad_out.scalar_type() == x.scalar_type(),
                 "batch_norm_bwd: grad_out must match x in shape and dtype");
     // Two passes, neither reads y: reduce(x, go) -> apply(x, go -> gx),
-    // each masking go by the activation recomputed from scale / shift.
+    // each scaling go by the activation's slope (a 0 / 1 mask for the
+    // clamps) recomputed from scale / shift.
     // With an addend (no activation) its gradient is grad_out itself.
     TORCH_CHECK(!grad_out2.has_value(),
                 "batch_norm_bwd: grad_out2 (the block-tail mailbox) is "
@@ -1448,7 +1458,8 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
         total_vec, (int)C);                                                 \
     CHECK_CUDA_OK();                                                        \
   } while (0)
-      if (act == BN_ACT_RELU6) BWD_ANYC(BN_ACT_RELU6);
+      if (act == BN_ACT_SILU) BWD_ANYC(BN_ACT_SILU);
+      else if (act == BN_ACT_RELU6) BWD_ANYC(BN_ACT_RELU6);
       else if (act == BN_ACT_RELU) BWD_ANYC(BN_ACT_RELU);
       else BWD_ANYC(BN_ACT_NONE);
 #undef BWD_ANYC

@@ -1,4 +1,4 @@
-// BatchNorm(+ReLU / ReLU6) kernels for any channel count (gfx950).
+// BatchNorm(+ReLU / ReLU6 / SiLU) kernels for any channel count (gfx950).
 //
 // batchnorm.hip's kernels take power-of-two C only: their channel-group
 // decompose is a mask.  MobileNetV2's widths (24, 96, 144, 160, 192, 320,
@@ -22,21 +22,41 @@
 //               [nparts][2C].  No atomics; two runs give the same bits.
 //   apply:      y = act(scale*x + shift (+ z)), two 16-byte streams in
 //               flight per thread.
-//   bwd reduce: sum(ghat), sum(ghat*xhat) with ghat = go masked by the
-//               activation, recomputed from the forward's scale / shift
-//               (the MASK 2 idea: no y read, no mask tensor).
-//   bwd apply:  gx = A*ghat + B*x + D with the same recomputed mask.
+//   bwd reduce: sum(ghat), sum(ghat*xhat) with ghat = go times the
+//               activation's slope, recomputed from the forward's scale /
+//               shift (the MASK 2 idea: no y read, no mask tensor).
+//   bwd apply:  gx = A*ghat + B*x + D with the same recomputed ghat.
 //
 // ReLU6 passes the gradient where 0 < v < 6.  Every kernel here forms the
 // pre-activation v through bn_anyc_v, a single explicit FMA: were it left
 // to the compiler's contraction, the forward, the backward reduce and the
 // backward apply could round v differently and disagree about an element
 // at a clamp boundary.
+//
+// SiLU (EfficientNet) has a slope where the clamps have a mask:
+//   y = v s,  ghat = go s (1 + v (1 - s)),  s = sigmoid(v) = 1 / (1 + e^-v).
+// bn_anyc_ghat is the one place that forms ghat for every activation, and
+// both backward kernels call it: the reduce and the apply then evaluate the
+// slope by the same instructions, so gw / gb and gx are gradients of one
+// ghat, bit for bit.  Every product on the way feeds an explicit fma or a
+// builtin, so none is left for the compiler to contract with a neighbour
+// (sa += ghat in the reduce would otherwise fuse ghat's last product into
+// the sum and skip its rounding, which the apply cannot do).
+// The exponential is the hardware's base-2 one (v_exp_f32, 1 ulp) on
+// fl(-v log2 e), the quotient v_rcp_f32 (1 ulp): e^-v is off by at most
+// (|v| + 2) 2^-24 relative (the rounded argument moves the exponent by
+// |v| 2^-24), s by 2^-23 more, the slope by less than (|v| + 6) 2^-24
+// absolute.  That absolute error does not shrink where the slope vanishes
+// (v = -1.278).  v far negative: 2^(-v log2 e) overflows to +inf past
+// v = -88.7, 1 + inf = inf, rcp(inf) = 0, so s = 0, y = v 0 = -0 and
+// ghat = go 0 (1 + v) = +-0: zeros, never inf - inf or 0 inf (v itself is
+// finite).  v far positive: e^-v flushes to 0, s = 1, y = v, slope 1.
 #pragma once
 
 #include "common.h"
 
-constexpr int BN_ACT_NONE = 0, BN_ACT_RELU = 1, BN_ACT_RELU6 = 2;
+constexpr int BN_ACT_NONE = 0, BN_ACT_RELU = 1, BN_ACT_RELU6 = 2,
+              BN_ACT_SILU = 3;
 
 __device__ __forceinline__ float bn_anyc_v(float sc, float xe, float sh) {
   return __builtin_fmaf(sc, xe, sh);
@@ -50,11 +70,31 @@ __device__ __forceinline__ bool bn_anyc_pass(float v) {
   return true;
 }
 
+// 1 / (1 + 2^fl(-v log2 e)); see the header for its error and its ends
+__device__ __forceinline__ float bn_anyc_sigmoid(float v) {
+  const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
+  return __builtin_amdgcn_rcpf(1.f + e);
+}
+
 template <int ACT>
 __device__ __forceinline__ float bn_anyc_act(float v) {
   if (ACT == BN_ACT_RELU) return fmaxf(v, 0.f);
   if (ACT == BN_ACT_RELU6) return fminf(fmaxf(v, 0.f), 6.f);
+  if (ACT == BN_ACT_SILU) return v * bn_anyc_sigmoid(v);
   return v;
+}
+
+// ghat = go times the activation's slope at pre-activation v.  The clamps
+// give go or 0.f untouched; SiLU's go * slope is an fma onto 0.f, a rounded
+// product that no caller's sum can absorb.
+template <int ACT>
+__device__ __forceinline__ float bn_anyc_ghat(float ge, float v) {
+  if (ACT == BN_ACT_SILU) {
+    const float s = bn_anyc_sigmoid(v);
+    const float slope = s * __builtin_fmaf(v, 1.f - s, 1.f);
+    return __builtin_fmaf(ge, slope, 0.f);
+  }
+  return bn_anyc_pass<ACT>(v) ? ge : 0.f;
 }
 
 // threads per block: the largest multiple of gpr that fits AMD_TPB
@@ -62,8 +102,7 @@ static inline int bn_anyc_block(int gpr) { return gpr * (AMD_TPB / gpr); }
 
 // ---- reduce: per-channel (a, b) sums over rows ----------------------------
 // fwd (BWD=false): a = x, b = x^2
-// bwd (BWD=true):  a = ghat, b = ghat * xhat,
-//                  ghat = go where the activation passes, else 0
+// bwd (BWD=true):  a = ghat, b = ghat * xhat, ghat = bn_anyc_ghat(go, v)
 // Two rows in flight per thread; they are accumulated in row order, so the
 // sums are those of the one-row-at-a-time loop.
 template <typename T, int VEC, bool BWD, int ACT>
@@ -104,9 +143,8 @@ bn_anyc_reduce_kernel(const T* __restrict__ x, const T* __restrict__ go,
       const float xe = to_f32(xv.v[k]);
       if (BWD) {
         float ge = to_f32(gv.v[k]);
-        if (ACT != BN_ACT_NONE &&
-            !bn_anyc_pass<ACT>(bn_anyc_v(sck[k], xe, shk[k])))
-          ge = 0.f;
+        if (ACT != BN_ACT_NONE)
+          ge = bn_anyc_ghat<ACT>(ge, bn_anyc_v(sck[k], xe, shk[k]));
         sa[k] += ge;
         sb[k] += ge * (xe - mk[k]) * ik[k];
       } else {
@@ -201,8 +239,8 @@ bn_anyc_apply_kernel(const T* __restrict__ x, const T* __restrict__ z,
 }
 
 // ---- bwd apply: gx = A*ghat + B*x + D -------------------------------------
-// ghat is go under the activation's mask, recomputed exactly as the reduce
-// did (bn_anyc_v); the contraction of the gx expression is spelled out so
+// ghat is go times the activation's slope, recomputed exactly as the reduce
+// did (bn_anyc_v, bn_anyc_ghat); the contraction of the gx expression is spelled out so
 // that it does not depend on the variant either.
 template <typename T, int VEC, int ACT>
 __global__ void __launch_bounds__(AMD_TPB)
@@ -241,8 +279,8 @@ bn_anyc_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ go,
       const float xe = to_f32(xv.v[k]), xe2 = to_f32(xv2.v[k]);
       float ge = to_f32(gv.v[k]), ge2 = to_f32(gv2.v[k]);
       if (ACT != BN_ACT_NONE) {
-        if (!bn_anyc_pass<ACT>(bn_anyc_v(rsc[k], xe, rsh[k]))) ge = 0.f;
-        if (!bn_anyc_pass<ACT>(bn_anyc_v(rsc[k], xe2, rsh[k]))) ge2 = 0.f;
+        ge = bn_anyc_ghat<ACT>(ge, bn_anyc_v(rsc[k], xe, rsh[k]));
+        ge2 = bn_anyc_ghat<ACT>(ge2, bn_anyc_v(rsc[k], xe2, rsh[k]));
       }
       out.v[k] = from_f32<T>(__builtin_fmaf(ra[k], ge, rb[k] * xe) + rd[k]);
       out2.v[k] =

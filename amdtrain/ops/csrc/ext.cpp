@@ -37,20 +37,23 @@ void multi_tensor_scale_check(std::vector<at::Tensor> tensors, double scale,
 void multi_tensor_cast(std::vector<at::Tensor> src,
                        std::vector<at::Tensor> dst);
 
-// batchnorm.hip (relu6, trailing and defaulted: ReLU6 in place of relu;
-// any channel count with whole 16-byte packs, at most 256 per row)
+// batchnorm.hip (relu6 and silu, trailing and defaulted: ReLU6 or SiLU in
+// place of relu; any channel count with whole 16-byte packs, at most 256 per
+// row)
 std::vector<at::Tensor> batch_norm_fwd_train(
     at::Tensor x, at::Tensor weight, at::Tensor bias, at::Tensor running_mean,
     at::Tensor running_var, double momentum, double eps, bool relu,
-    std::optional<at::Tensor> addend, bool relu6);
+    std::optional<at::Tensor> addend, bool relu6, bool silu);
 std::vector<at::Tensor> batch_norm_fwd_train_from_parts(
     at::Tensor x, at::Tensor parts, at::Tensor weight, at::Tensor bias,
     at::Tensor running_mean, at::Tensor running_var, double momentum,
-    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6);
+    double eps, bool relu, std::optional<at::Tensor> addend, bool relu6,
+    bool silu);
 at::Tensor batch_norm_fwd_eval(at::Tensor x, at::Tensor weight,
                                at::Tensor bias, at::Tensor running_mean,
                                at::Tensor running_var, double eps, bool relu,
-                               std::optional<at::Tensor> addend, bool relu6);
+                               std::optional<at::Tensor> addend, bool relu6,
+                               bool silu);
 at::Tensor bn_collapse_partials(at::Tensor parts, long impl);
 std::vector<at::Tensor> batch_norm_train_stats(
     at::Tensor x, std::optional<at::Tensor> parts, at::Tensor weight,
@@ -77,7 +80,8 @@ std::vector<at::Tensor> batch_norm_bwd(at::Tensor x, at::Tensor grad_out,
                                        std::optional<at::Tensor> shift,
                                        std::optional<at::Tensor> grad_out2,
                                        std::optional<at::Tensor> relu_mask,
-                                       bool grad_out2_compact, bool relu6);
+                                       bool grad_out2_compact, bool relu6,
+                                       bool silu);
 std::vector<at::Tensor> batch_norm_bwd_pool(
     at::Tensor x, at::Tensor grad_pool, std::optional<at::Tensor> grad_pool2,
     at::Tensor idx, at::Tensor weight, at::Tensor mean, at::Tensor invstd,
@@ -174,18 +178,21 @@ at::Tensor dwconv5x5_dgrad(at::Tensor dy2d, long Nn, long H, long W,
 at::Tensor dwconv5x5_wgrad(at::Tensor dy2d, at::Tensor x2d, long Nn, long H,
                            long W, long stride);
 
-// se.hip
+// se.hip (hidden_act: 0 ReLU, 1 SiLU, which adds z1 to se_excite's outputs
+// and takes it as se_excite_bwd's h; gate: 0 hardsigmoid, 1 sigmoid)
 at::Tensor se_squeeze(at::Tensor x2d, long N, long HW, bool hswish,
                       long splits);
 std::vector<at::Tensor> se_excite(at::Tensor part, long HW, at::Tensor w1,
-                                  at::Tensor b1, at::Tensor w2, at::Tensor b2);
+                                  at::Tensor b1, at::Tensor w2, at::Tensor b2,
+                                  long hidden_act, long gate);
 at::Tensor se_scale(at::Tensor x2d, at::Tensor s, long N, long HW,
                     bool hswish);
 at::Tensor se_bwd_reduce(at::Tensor dy2d, at::Tensor x2d, long N, long HW,
                          bool hswish, long splits);
 std::vector<at::Tensor> se_excite_bwd(at::Tensor ds_part, at::Tensor s,
                                       at::Tensor h, at::Tensor w1,
-                                      at::Tensor w2, long HW);
+                                      at::Tensor w2, long HW,
+                                      long hidden_act, long gate);
 std::vector<at::Tensor> se_wgrad(at::Tensor dz2, at::Tensor dz1,
                                  at::Tensor mean, at::Tensor h);
 at::Tensor se_bwd_apply(at::Tensor dy2d, at::Tensor x2d, at::Tensor s,
@@ -210,17 +217,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
         py::arg("eps"), py::arg("relu"),
-        py::arg("addend") = std::nullopt, py::arg("relu6") = false);
+        py::arg("addend") = std::nullopt, py::arg("relu6") = false,
+        py::arg("silu") = false);
   m.def("batch_norm_fwd_train_from_parts", &batch_norm_fwd_train_from_parts,
         py::arg("x"), py::arg("parts"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
         py::arg("eps"), py::arg("relu"), py::arg("addend") = std::nullopt,
-        py::arg("relu6") = false);
+        py::arg("relu6") = false, py::arg("silu") = false);
   m.def("batch_norm_fwd_eval", &batch_norm_fwd_eval,
         py::arg("x"), py::arg("weight"), py::arg("bias"),
         py::arg("running_mean"), py::arg("running_var"), py::arg("eps"),
         py::arg("relu"), py::arg("addend") = std::nullopt,
-        py::arg("relu6") = false);
+        py::arg("relu6") = false, py::arg("silu") = false);
   m.def("batch_norm_train_stats", &batch_norm_train_stats);
   // impl: 1 streaming fold, 0 the kernel it replaced, -1 =
   // AMDTRAIN_BN_COLLAPSE or 1
@@ -234,7 +242,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = std::nullopt, py::arg("shift") = std::nullopt,
         py::arg("grad_out2") = std::nullopt,
         py::arg("relu_mask") = std::nullopt,
-        py::arg("grad_out2_compact") = false, py::arg("relu6") = false);
+        py::arg("grad_out2_compact") = false, py::arg("relu6") = false,
+        py::arg("silu") = false);
   m.def("batch_norm_bwd_pool", &batch_norm_bwd_pool, py::arg("x"),
         py::arg("grad_pool"), py::arg("grad_pool2"), py::arg("idx"),
         py::arg("weight"), py::arg("mean"), py::arg("invstd"),
@@ -318,14 +327,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_squeeze", &se_squeeze, py::arg("x2d"), py::arg("N"),
         py::arg("HW"), py::arg("hswish"), py::arg("splits") = 0);
   m.def("se_excite", &se_excite, py::arg("part"), py::arg("HW"),
-        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"));
+        py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+        py::arg("hidden_act") = 0, py::arg("gate") = 0);
   m.def("se_scale", &se_scale, py::arg("x2d"), py::arg("s"), py::arg("N"),
         py::arg("HW"), py::arg("hswish"));
   m.def("se_bwd_reduce", &se_bwd_reduce, py::arg("dy2d"), py::arg("x2d"),
         py::arg("N"), py::arg("HW"), py::arg("hswish"),
         py::arg("splits") = 0);
   m.def("se_excite_bwd", &se_excite_bwd, py::arg("ds_part"), py::arg("s"),
-        py::arg("h"), py::arg("w1"), py::arg("w2"), py::arg("HW"));
+        py::arg("h"), py::arg("w1"), py::arg("w2"), py::arg("HW"),
+        py::arg("hidden_act") = 0, py::arg("gate") = 0);
   m.def("se_wgrad", &se_wgrad, py::arg("dz2"), py::arg("dz1"),
         py::arg("mean"), py::arg("h"));
   m.def("se_bwd_apply", &se_bwd_apply, py::arg("dy2d"), py::arg("x2d"),

@@ -1,8 +1,11 @@
-// Squeeze-excite and hardswish for gfx950 (MobileNetV3): NHWC bf16/fp16
-// activations as rows [R = N*HW, C], fp32 weights and statistics.
+// Squeeze-excite and hardswish for gfx950 (MobileNetV3, EfficientNet): NHWC
+// bf16/fp16 activations as rows [R = N*HW, C], fp32 weights and statistics.
 //
-//   y = a(x) * s[n, c],  s = hardsigmoid(W2 . relu(W1 . mean_hw(a(x)) + b1) + b2)
+//   y = a(x) * s[n, c],  s = gate(W2 . hid(W1 . mean_hw(a(x)) + b1) + b2)
 //
+// hid is ReLU or SiLU, gate is hardsigmoid or sigmoid (template parameters
+// HID, GATE of the two MLP kernels): MobileNetV3 is ReLU + hardsigmoid,
+// EfficientNet SiLU + sigmoid.
 // a is the identity or hardswish (template parameter HSW): with HSW the
 // input is the linear BN output and the activation is never written.  The
 // op is pure HBM traffic around a tiny MLP, so the design is about touching
@@ -36,6 +39,18 @@
 // at x = 3, on bf16 inputs that land there as on any other.
 // The hardsigmoid gate's derivative is 1/6 strictly inside (0 < s < 1) and
 // 0 where it saturates, torch's convention again.
+//
+// The sigmoid gate's slope s (1 - s) comes from the saved s.  A SiLU hidden
+// unit's slope sg (1 + z1 (1 - sg)), sg = sigmoid(z1), cannot be had from
+// h = z1 sg (h is not monotone in z1), so the forward keeps the
+// pre-activation as well: under SiLU se_excite returns z1 [N, Cs] as a
+// fourth tensor and se_excite_bwd takes it where ReLU passes h.  A second
+// [N, Cs] fp32 tensor (48 KiB at N = 256, Cs = 48) rather than z1 alone with
+// h recomputed in se_wgrad: there every thread of a dW2 row would redo the
+// same N sigmoids, C times over, to save a tensor a thousandth of x's size.
+// sigmoid(z) = 1 / (1 + 2^fl(-z log2 e)) on v_exp_f32 and v_rcp_f32 (1 ulp
+// each; batchnorm_anyc.h has the error account): z far negative gives
+// 2^.. = inf, s = 0 and slope 0, never NaN.
 #include "common.h"
 
 // No packed-fp32 selection (v_pk_*_f32) for the code of this file (see
@@ -66,6 +81,14 @@ __device__ __forceinline__ float hsw(float x) {
 __device__ __forceinline__ float hsw_grad(float x) {
   const float mid = __builtin_fmaf(x, 1.f / 3.f, 0.5f);
   return x <= -3.f ? 0.f : (x >= 3.f ? 1.f : mid);
+}
+
+constexpr int SE_HID_RELU = 0, SE_HID_SILU = 1;
+constexpr int SE_GATE_HSIG = 0, SE_GATE_SIGMOID = 1;
+
+__device__ __forceinline__ float se_sigmoid(float z) {
+  const float e = __builtin_amdgcn_exp2f(z * -1.44269504088896341f);
+  return __builtin_amdgcn_rcpf(1.f + e);
 }
 
 template <bool HSW> __device__ __forceinline__ float se_act(float x) {
@@ -251,13 +274,16 @@ __device__ __forceinline__ void se_matTvec(const float* __restrict__ M,
   }
 }
 
-// one block per image: mean, h = relu(W1 mean + b1), s = hsig(W2 h + b2)
+// one block per image: mean, z1 = W1 mean + b1, h = hid(z1),
+// s = gate(W2 h + b2); z1 is written under SiLU only
+template <int HID, int GATE>
 __global__ void __launch_bounds__(SE_MLP_TPB)
 se_excite_kernel(const float* __restrict__ part, const float* __restrict__ w1,
                  const float* __restrict__ b1, const float* __restrict__ w2,
                  const float* __restrict__ b2, float* __restrict__ s_out,
                  float* __restrict__ mean_out, float* __restrict__ h_out,
-                 int S, int C, int Cs, float inv_hw) {
+                 float* __restrict__ z1_out, int S, int C, int Cs,
+                 float inv_hw) {
   extern __shared__ float sm[];  // mean[C], h[Cs]
   float* mean = sm;
   float* h = sm + C;
@@ -271,21 +297,31 @@ se_excite_kernel(const float* __restrict__ part, const float* __restrict__ w1,
   }
   se_barrier();
   se_matvec(w1, mean, Cs, C, [&](int j, float a) {
-    a = fmaxf(a + b1[j], 0.f);
+    if (HID == SE_HID_SILU) {
+      a += b1[j];
+      z1_out[n * Cs + j] = a;
+      a *= se_sigmoid(a);
+    } else {
+      a = fmaxf(a + b1[j], 0.f);
+    }
     h[j] = a;
     h_out[n * Cs + j] = a;
   });
   se_barrier();
   se_matvec(w2, h, C, Cs, [&](int c, float a) {
     a += b2[c];
-    s_out[n * C + c] = fminf(fmaxf(a + 3.f, 0.f), 6.f) * (1.f / 6.f);
+    s_out[n * C + c] = GATE == SE_GATE_SIGMOID
+                           ? se_sigmoid(a)
+                           : fminf(fmaxf(a + 3.f, 0.f), 6.f) * (1.f / 6.f);
   });
 }
 
-// one block per image: ds -> dz2 -> dz1 -> dm
+// one block per image: ds -> dz2 -> dz1 -> dm.  hz is h under ReLU (a
+// mask) and z1 under SiLU (a slope).
+template <int HID, int GATE>
 __global__ void __launch_bounds__(SE_MLP_TPB)
 se_excite_bwd_kernel(const float* __restrict__ ds_part,
-                     const float* __restrict__ s, const float* __restrict__ h,
+                     const float* __restrict__ s, const float* __restrict__ hz,
                      const float* __restrict__ w1, const float* __restrict__ w2,
                      float* __restrict__ dz2_out, float* __restrict__ dz1_out,
                      float* __restrict__ dm_out, int S, int C, int Cs,
@@ -299,14 +335,24 @@ se_excite_bwd_kernel(const float* __restrict__ ds_part,
     float a = 0.f;
     for (int sp = 0; sp < S; ++sp) a += ds_part[(n * S + sp) * C + c];
     const float sv = s[n * C + c];
-    a = (sv > 0.f && sv < 1.f) ? a * (1.f / 6.f) : 0.f;
+    if (GATE == SE_GATE_SIGMOID)
+      a *= sv * (1.f - sv);
+    else
+      a = (sv > 0.f && sv < 1.f) ? a * (1.f / 6.f) : 0.f;
     dz2[c] = a;
     dz2_out[n * C + c] = a;
   }
   se_barrier();
-  // dz1 = (W2^T dz2) masked by h > 0;  W2 is [C][Cs]
+  // dz1 = (W2^T dz2) times hid'(z1): the mask h > 0, or SiLU's slope;
+  // W2 is [C][Cs]
   se_matTvec(w2, dz2, Cs, C, red, [&](int j, float a) {
-    a = h[n * Cs + j] > 0.f ? a : 0.f;
+    const float q = hz[n * Cs + j];
+    if (HID == SE_HID_SILU) {
+      const float sg = se_sigmoid(q);
+      a *= sg * __builtin_fmaf(q, 1.f - sg, 1.f);
+    } else {
+      a = q > 0.f ? a : 0.f;
+    }
     dz1[j] = a;
     dz1_out[n * Cs + j] = a;
   });
@@ -451,6 +497,28 @@ static void se_check_cs(const char* op, long Cs) {
               ": squeeze width must be in [1, 1024] (Cs = ", Cs, ")");
 }
 
+// hidden_act: 0 ReLU, 1 SiLU;  gate: 0 hardsigmoid, 1 sigmoid
+static void se_check_acts(const char* op, long hidden_act, long gate) {
+  TORCH_CHECK((hidden_act == SE_HID_RELU || hidden_act == SE_HID_SILU) &&
+                  (gate == SE_GATE_HSIG || gate == SE_GATE_SIGMOID),
+              op, ": hidden_act and gate must be 0 or 1, got ", hidden_act,
+              ", ", gate);
+}
+
+// calls fn with (HID, GATE) as integral constants
+template <typename F>
+static void se_by_acts(long hidden_act, long gate, F fn) {
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  if (hidden_act == SE_HID_SILU) {
+    if (gate == SE_GATE_SIGMOID) fn(I1{}, I1{});
+    else fn(I1{}, I0{});
+  } else {
+    if (gate == SE_GATE_SIGMOID) fn(I0{}, I1{});
+    else fn(I0{}, I0{});
+  }
+}
+
 // row splits of the reduce kernels: enough blocks to fill the chip, at
 // least two rows per slot and split
 static int se_splits(long N, long HW, const SeGeo& g, long splits) {
@@ -557,10 +625,12 @@ at::Tensor se_bwd_reduce(at::Tensor dy2d, at::Tensor x2d, long N, long HW,
   return se_reduce<true>("se_bwd_reduce", x2d, &dy2d, N, HW, hswish, splits);
 }
 
-// {s [N, C], mean [N, C], h [N, Cs]} from the squeeze partials
+// {s [N, C], mean [N, C], h [N, Cs]} from the squeeze partials, and
+// z1 [N, Cs] as a fourth under a SiLU hidden layer
 std::vector<at::Tensor> se_excite(at::Tensor part, long HW, at::Tensor w1,
-                                  at::Tensor b1, at::Tensor w2,
-                                  at::Tensor b2) {
+                                  at::Tensor b1, at::Tensor w2, at::Tensor b2,
+                                  long hidden_act, long gate) {
+  se_check_acts("se_excite", hidden_act, gate);
   TORCH_CHECK(part.is_cuda() && part.dim() == 3 && part.is_contiguous() &&
                   part.scalar_type() == at::kFloat,
               "se_excite: partials must be dense fp32 [N, S, C]");
@@ -577,17 +647,25 @@ std::vector<at::Tensor> se_excite(at::Tensor part, long HW, at::Tensor w1,
   auto s = at::empty({N, C}, part.options());
   auto mean = at::empty({N, C}, part.options());
   auto h = at::empty({N, Cs}, part.options());
-  if (N == 0) return {s, mean, h};
+  const bool silu = hidden_act == SE_HID_SILU;
+  at::Tensor z1;
+  if (silu) z1 = at::empty({N, Cs}, part.options());
+  std::vector<at::Tensor> out = {s, mean, h};
+  if (silu) out.push_back(z1);
+  if (N == 0) return out;
   auto stream = at::cuda::getCurrentCUDAStream();
-  se_excite_kernel<<<(unsigned)N, SE_MLP_TPB, (C + Cs) * sizeof(float),
-                     stream>>>(
-      part.data_ptr<float>(), w1.data_ptr<float>(),
-      b1.data_ptr<float>(), w2.data_ptr<float>(),
-      b2.data_ptr<float>(), s.data_ptr<float>(),
-      mean.data_ptr<float>(), h.data_ptr<float>(), (int)S, (int)C, (int)Cs,
-      1.f / (float)HW);
+  se_by_acts(hidden_act, gate, [&](auto hid, auto gt) {
+    se_excite_kernel<decltype(hid)::value, decltype(gt)::value>
+        <<<(unsigned)N, SE_MLP_TPB, (C + Cs) * sizeof(float), stream>>>(
+            part.data_ptr<float>(), w1.data_ptr<float>(),
+            b1.data_ptr<float>(), w2.data_ptr<float>(),
+            b2.data_ptr<float>(), s.data_ptr<float>(),
+            mean.data_ptr<float>(), h.data_ptr<float>(),
+            silu ? z1.data_ptr<float>() : nullptr, (int)S, (int)C, (int)Cs,
+            1.f / (float)HW);
+  });
   CHECK_CUDA_OK();
-  return {s, mean, h};
+  return out;
 }
 
 at::Tensor se_scale(at::Tensor x2d, at::Tensor s, long N, long HW,
@@ -595,10 +673,13 @@ at::Tensor se_scale(at::Tensor x2d, at::Tensor s, long N, long HW,
   return se_apply<false>("se_scale", x2d, nullptr, s, nullptr, N, HW, hswish);
 }
 
-// {dz2 [N, C], dz1 [N, Cs], dm [N, C] (already / HW)}
+// {dz2 [N, C], dz1 [N, Cs], dm [N, C] (already / HW)}; h is the forward's
+// h under ReLU and its z1 under SiLU
 std::vector<at::Tensor> se_excite_bwd(at::Tensor ds_part, at::Tensor s,
                                       at::Tensor h, at::Tensor w1,
-                                      at::Tensor w2, long HW) {
+                                      at::Tensor w2, long HW,
+                                      long hidden_act, long gate) {
+  se_check_acts("se_excite_bwd", hidden_act, gate);
   TORCH_CHECK(ds_part.is_cuda() && ds_part.dim() == 3 &&
                   ds_part.is_contiguous() &&
                   ds_part.scalar_type() == at::kFloat,
@@ -618,13 +699,16 @@ std::vector<at::Tensor> se_excite_bwd(at::Tensor ds_part, at::Tensor s,
   auto dm = at::empty({N, C}, ds_part.options());
   if (N == 0) return {dz2, dz1, dm};
   auto stream = at::cuda::getCurrentCUDAStream();
-  se_excite_bwd_kernel<<<(unsigned)N, SE_MLP_TPB,
-                         (C + Cs + SE_MLP_TPB) * sizeof(float), stream>>>(
-      ds_part.data_ptr<float>(), s.data_ptr<float>(),
-      h.data_ptr<float>(), w1.data_ptr<float>(),
-      w2.data_ptr<float>(), dz2.data_ptr<float>(),
-      dz1.data_ptr<float>(), dm.data_ptr<float>(), (int)S, (int)C, (int)Cs,
-      1.f / (float)HW);
+  se_by_acts(hidden_act, gate, [&](auto hid, auto gt) {
+    se_excite_bwd_kernel<decltype(hid)::value, decltype(gt)::value>
+        <<<(unsigned)N, SE_MLP_TPB, (C + Cs + SE_MLP_TPB) * sizeof(float),
+           stream>>>(
+            ds_part.data_ptr<float>(), s.data_ptr<float>(),
+            h.data_ptr<float>(), w1.data_ptr<float>(),
+            w2.data_ptr<float>(), dz2.data_ptr<float>(),
+            dz1.data_ptr<float>(), dm.data_ptr<float>(), (int)S, (int)C,
+            (int)Cs, 1.f / (float)HW);
+  });
   CHECK_CUDA_OK();
   return {dz2, dz1, dm};
 }

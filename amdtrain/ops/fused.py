@@ -1,4 +1,4 @@
-"""Model-facing fused NHWC ops: BatchNorm(+add)(+ReLU/ReLU6), pooling.
+"""Model-facing fused NHWC ops: BatchNorm(+add)(+ReLU/ReLU6/SiLU), pooling.
 
 The reference runs BN and ReLU as separate cuDNN/elementwise kernels after
 every conv (53 BN layers in ResNet-50) — on MI355X that is pure
@@ -26,26 +26,26 @@ __all__ = ["batch_norm", "bn_relu6_fusable", "bn_add_relu", "bn_add_relu_downsam
 
 
 class _BNFunction(torch.autograd.Function):
-    """Fused BN(+add)(+ReLU/ReLU6) training-mode forward/backward on NHWC
+    """Fused BN(+add)(+ReLU/ReLU6/SiLU) training-mode forward/backward on NHWC
     GPU tensors.  When the producing conv attached per-block statistics
     partials (conv epilogue fusion), the reduce pass over x is skipped."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
                 momentum, eps, relu, addend, parts, res_cell=None,
-                relu6=False):
+                relu6=False, silu=False):
         e = require_ext()
         if parts is not None:
             y, mean, invstd, scale, shift, mask = \
                 e.batch_norm_fwd_train_from_parts(
                     x, parts, weight, bias, running_mean, running_var,
                     float(momentum), float(eps), bool(relu), addend,
-                    bool(relu6))
+                    bool(relu6), bool(silu))
         else:
             y, mean, invstd, scale, shift, mask = e.batch_norm_fwd_train(
                 x, weight, bias, running_mean, running_var,
                 float(momentum), float(eps), bool(relu), addend,
-                bool(relu6))
+                bool(relu6), bool(silu))
         # scale/shift ([C] fp32) let the bwd recompute the relu mask as
         # scale*x+shift>0 for addend-free BNs; block-tail BNs save the
         # fwd-computed 1-bit relu mask instead (bwd skips the y read)
@@ -53,6 +53,7 @@ class _BNFunction(torch.autograd.Function):
                               mask)
         ctx.relu = bool(relu)
         ctx.relu6 = bool(relu6)
+        ctx.silu = bool(silu)
         ctx.has_addend = addend is not None
         # block-tail BN grad mailbox (see batch_norm below): our backward
         # folds a rerouted shortcut gradient into the reduce as a second
@@ -79,10 +80,10 @@ class _BNFunction(torch.autograd.Function):
         grad_x, grad_w, grad_b, ghat = e.batch_norm_bwd(
             x, grad_out.contiguous(memory_format=torch.channels_last),
             y, weight, mean, invstd, ctx.relu, ctx.has_addend,
-            scale, shift, go2, mask, compact, ctx.relu6)
+            scale, shift, go2, mask, compact, ctx.relu6, ctx.silu)
         grad_addend = ghat if ctx.has_addend else None
         return (grad_x, grad_w, grad_b, None, None, None, None, None,
-                grad_addend, None, None, None)
+                grad_addend, None, None, None, None)
 
 
 def _bn_torch(x: torch.Tensor, bn, relu: bool,
@@ -118,11 +119,18 @@ def bn_relu6_fusable(x: torch.Tensor) -> bool:
     return not use_ext_for(x) or _anyc_ok(x)
 
 
+def _bn_silu_enabled() -> bool:
+    """AMDTRAIN_BN_SILU=0 (A/B baseline; read on every call) runs
+    ``batch_norm(silu=True)`` as the linear BN kernels followed by
+    ``F.silu``."""
+    return os.environ.get("AMDTRAIN_BN_SILU", "1") == "1"
+
+
 def batch_norm(x: torch.Tensor, bn, relu: bool = False,
                addend: Optional[torch.Tensor] = None,
-               relu6: bool = False) -> torch.Tensor:
+               relu6: bool = False, silu: bool = False) -> torch.Tensor:
     """BatchNorm2d through module ``bn``'s parameters/buffers, optionally fused
-    with a residual add and/or ReLU, or with ReLU6 (no addend).
+    with a residual add and/or ReLU, or with ReLU6 or SiLU (no addend).
 
     On the GPU a power-of-two C without ReLU6 runs on the kernels it always
     did.  Any other C inside ``_anyc_ok``, and every ReLU6, runs on the any-C
@@ -130,17 +138,24 @@ def batch_norm(x: torch.Tensor, bn, relu: bool = False,
     only).  Without ReLU6, what is left takes the library BN as it always
     did.  ReLU6 outside ``_anyc_ok`` (C % VEC != 0, or more than 256 packs
     per row such as fp32 C = 1280) has no kernel and is an error here, not a
-    library composition: see ``bn_relu6_fusable``."""
+    library composition: see ``bn_relu6_fusable``.  SiLU routes and raises
+    exactly as ReLU6 does; off the extension it is ``F.silu`` on the
+    plain-torch BN."""
     if relu and relu6:
         raise ValueError("batch_norm: relu and relu6 are mutually exclusive")
     if relu6 and addend is not None:
         raise ValueError("batch_norm: relu6 with an addend is not supported")
+    if silu and (relu or relu6 or addend is not None):
+        raise ValueError("batch_norm: silu excludes relu, relu6 and an addend")
     C = x.size(1)
     pow2 = (C & (C - 1)) == 0
     on_ext = use_ext_for(x)
-    if on_ext and relu6 and not _anyc_ok(x):
+    if on_ext and silu and not _bn_silu_enabled():
+        return F.silu(batch_norm(x, bn))
+    if on_ext and (relu6 or silu) and not _anyc_ok(x):
         raise NotImplementedError(
-            f"batch_norm: no ReLU6 kernel for C = {C} in {x.dtype} (needs "
+            f"batch_norm: no {'SiLU' if silu else 'ReLU6'} kernel for "
+            f"C = {C} in {x.dtype} (needs "
             f"whole 16-byte packs, at most 256 per row)")
     if on_ext and not pow2:
         on_ext = _anyc_ok(x) and not (relu and addend is not None)
@@ -161,14 +176,15 @@ def batch_norm(x: torch.Tensor, bn, relu: bool = False,
                                    and _vec_ok(xc, 256))
             out = _BNFunction.apply(xc, bn.weight, bn.bias, bn.running_mean,
                                     bn.running_var, bn.momentum, bn.eps,
-                                    relu, ac, parts, cell, relu6)
+                                    relu, ac, parts, cell, relu6, silu)
             if cell is not None:
                 out._amdtrain_next_cell = cell
             return out
         return require_ext().batch_norm_fwd_eval(
             xc, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-            float(bn.eps), bool(relu), ac, bool(relu6))
-    return _bn_torch(x, bn, relu, addend, relu6)
+            float(bn.eps), bool(relu), ac, bool(relu6), bool(silu))
+    y = _bn_torch(x, bn, relu, addend, relu6)
+    return F.silu(y) if silu else y
 
 
 def bn_add_relu(x: torch.Tensor, bn, addend: torch.Tensor) -> torch.Tensor:
