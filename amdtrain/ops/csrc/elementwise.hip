@@ -67,11 +67,16 @@ topk_ranks_kernel(const T* __restrict__ logits, const long* __restrict__ target,
   const T* x = logits + row * C;
   const long tidx = target[row];
   const float tv = to_f32(x[tidx]);
+  const bool tnan = tv != tv;
   float cnt = 0.f;
   for (long c = lane; c < C; c += AMD_WAVE) {
     float v = to_f32(x[c]);
-    // rank rule: higher value first; ties broken by lower index
-    cnt += (v > tv || (v == tv && c < tidx)) ? 1.f : 0.f;
+    // rank rule (a stable descending sort): NaN ranks above every number,
+    // then higher value first; ties, NaN among NaN too, by lower index
+    const bool vnan = v != v;
+    const bool before = tnan ? (vnan && c < tidx)
+                             : (vnan || v > tv || (v == tv && c < tidx));
+    cnt += before ? 1.f : 0.f;
   }
   cnt = wave_reduce_sum(cnt);
   if (lane == 0) ranks[row] = (int)cnt;

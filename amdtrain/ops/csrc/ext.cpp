@@ -24,7 +24,8 @@ at::Tensor multi_tensor_lars(std::vector<at::Tensor> params,
 // cross_entropy.hip
 std::vector<at::Tensor> cross_entropy_fwd(at::Tensor logits, at::Tensor target);
 at::Tensor cross_entropy_bwd(at::Tensor logits, at::Tensor target,
-                             at::Tensor lse, at::Tensor upstream);
+                             at::Tensor lse, at::Tensor lse_lo,
+                             at::Tensor upstream);
 
 // elementwise.hip
 at::Tensor normalize_u8(at::Tensor x, std::vector<double> mean,

@@ -61,12 +61,23 @@ maxpool_fwd_kernel(const T* __restrict__ x, T* __restrict__ y,
           if (BNRELU)
             v = to_f32(from_f32<T>(
                 fmaxf(sm[c0 + k] * v + sm[C + c0 + k], 0.f)));
-          if (v > best[k]) {
+          // a NaN tap wins and then stays (nothing compares above it);
+          // the fused taps are fmaxf(.., 0) and never NaN
+          if (v > best[k] || (!BNRELU && v != v)) {
             best[k] = v;
             bidx[k] = (unsigned char)(kh * 3 + kw);
           }
         }
       }
+    }
+    // no tap beat the -inf start: the window is all -inf and its gradient
+    // goes to the first tap inside the image (fused taps are >= 0)
+    if (!BNRELU) {
+      const unsigned char first =
+          (unsigned char)((h0 < 0 ? 3 : 0) + (w0 < 0 ? 1 : 0));
+#pragma unroll
+      for (int k = 0; k < VEC; ++k)
+        if (bidx[k] == 255) bidx[k] = first;
     }
     const long obase = ((n * Ho + ho) * Wo + wo) * C + c0;
     Pack<T, VEC> yv;
@@ -181,6 +192,14 @@ static void check_nhwc4(const at::Tensor& x) {
               "expected NHWC CUDA tensor");
 }
 
+// every kernel here moves whole 16-byte packs of channels: with a partial
+// pack the last C % VEC channels would never be written, and C < VEC is an
+// empty grid
+static void check_packs(long C, int vec, const char* op) {
+  TORCH_CHECK(C % vec == 0, op, ": C = ", C, " is not a multiple of ", vec,
+              " (one 16-byte pack of this dtype)");
+}
+
 }  // namespace
 
 // scale/shift given: the stem BN+ReLU is applied per tap inside the pool
@@ -210,7 +229,7 @@ std::vector<at::Tensor> max_pool_3x3_s2_fwd(at::Tensor x,
       "maxpool_fwd", [&] {
         using devT = typename DevT<scalar_t>::type;
         constexpr int VEC = 16 / sizeof(devT);
-        TORCH_CHECK(C % VEC == 0);
+        check_packs(C, VEC, "max_pool_3x3_s2_fwd");
         long total = N * Ho * Wo * (C / VEC);
         if (bnrelu)
           maxpool_fwd_kernel<devT, VEC, true>
@@ -244,6 +263,7 @@ at::Tensor max_pool_3x3_s2_bwd(at::Tensor grad_y, at::Tensor idx, long H,
       "maxpool_bwd", [&] {
         using devT = typename DevT<scalar_t>::type;
         constexpr int VEC = 16 / sizeof(devT);
+        check_packs(C, VEC, "max_pool_3x3_s2_bwd");
         long total = N * H * W * (C / VEC);
         maxpool_bwd_kernel<devT, VEC>
             <<<amd_grid(total), AMD_TPB, 0, stream>>>(
@@ -266,6 +286,7 @@ at::Tensor global_avg_pool_fwd(at::Tensor x) {
       "gap_fwd", [&] {
         using devT = typename DevT<scalar_t>::type;
         constexpr int VEC = 16 / sizeof(devT);
+        check_packs(C, VEC, "global_avg_pool_fwd");
         long total = N * (C / VEC);
         gap_fwd_kernel<devT, VEC><<<amd_grid(total), AMD_TPB, 0, stream>>>(
             (const devT*)x.const_data_ptr(), (devT*)y.data_ptr(), N,
@@ -288,6 +309,7 @@ at::Tensor global_avg_pool_bwd(at::Tensor grad_y, long H, long W) {
       "gap_bwd", [&] {
         using devT = typename DevT<scalar_t>::type;
         constexpr int VEC = 16 / sizeof(devT);
+        check_packs(C, VEC, "global_avg_pool_bwd");
         long total = N * H * W * (C / VEC);
         gap_bwd_kernel<devT, VEC><<<amd_grid(total), AMD_TPB, 0, stream>>>(
             (const devT*)g.const_data_ptr(), (devT*)gx.data_ptr(), N,

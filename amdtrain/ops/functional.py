@@ -35,16 +35,17 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits: torch.Tensor, target: torch.Tensor):
         e = require_ext()
-        losses, lse = e.cross_entropy_fwd(logits, target)
-        ctx.save_for_backward(logits, target, lse)
+        # lse + lse_lo: the per-row logsumexp as an fp32 pair
+        losses, lse, lse_lo = e.cross_entropy_fwd(logits, target)
+        ctx.save_for_backward(logits, target, lse, lse_lo)
         return losses.mean()
 
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
-        logits, target, lse = ctx.saved_tensors
+        logits, target, lse, lse_lo = ctx.saved_tensors
         e = require_ext()
         # upstream grad stays on device: no host sync per backward
-        grad_logits = e.cross_entropy_bwd(logits, target, lse,
+        grad_logits = e.cross_entropy_bwd(logits, target, lse, lse_lo,
                                           grad_out.reshape(1))
         return grad_logits, None
 
@@ -64,17 +65,22 @@ def topk_ranks(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Rank of the true class in the sorted (desc, first-occurrence) logits.
 
     rank r means the label would appear at position r in ``topk`` output,
-    so correct@k == (rank < k).
+    so correct@k == (rank < k).  The order is that of a stable descending
+    sort: NaN ranks above every number, then +inf down to -inf, and equal
+    values, NaN among NaN too, by lower index.  An all-NaN row therefore
+    gives rank == label, not 0.
     """
     if use_ext_for(logits):
         return require_ext().topk_ranks(logits, target)
     with torch.no_grad():
-        tv = logits.gather(1, target.reshape(-1, 1))  # [B,1]
-        greater = (logits > tv).sum(dim=1)
-        # ties broken by index order (torch.topk returns lower index first)
+        t = target.reshape(-1, 1).long()
+        tv = logits.gather(1, t)  # [B,1]
+        nan, tnan = logits.isnan(), tv.isnan()
+        greater = (logits > tv) | (nan & ~tnan)
+        tie = (logits == tv) | (nan & tnan)
         idx = torch.arange(logits.size(1), device=logits.device)
-        tie_before = ((logits == tv) & (idx.unsqueeze(0) < target.reshape(-1, 1))).sum(dim=1)
-        return (greater + tie_before).to(torch.int32)
+        before = greater | (tie & (idx.unsqueeze(0) < t))
+        return before.sum(dim=1).to(torch.int32)
 
 
 def topk_correct_counts(logits: torch.Tensor, target: torch.Tensor,

@@ -398,7 +398,9 @@ class _GlobalAvgPool(torch.autograd.Function):
 
 
 def global_avg_pool(x: torch.Tensor) -> torch.Tensor:
-    """Global average pool to [N,C,1,1] (AdaptiveAvgPool2d((1,1)) parity)."""
-    if use_ext_for(x):
+    """Global average pool to [N,C,1,1] (AdaptiveAvgPool2d((1,1)) parity).
+    The kernels move whole 16-byte packs of channels; any other C (no model
+    in the registry has one) takes the torch op."""
+    if use_ext_for(x) and x.size(1) % (16 // x.element_size()) == 0:
         return _GlobalAvgPool.apply(x.contiguous(memory_format=torch.channels_last))
     return F.adaptive_avg_pool2d(x, (1, 1))
