@@ -882,6 +882,67 @@ def conv_stem_mfma(x: torch.Tensor, weight: torch.Tensor, stride: int,
     return y
 
 
+def _stem3x3_mode() -> str:
+    """AMDTRAIN_STEM3X3, read per call: unset -> the direct RGB stem kernels
+    (stem3x3.hip) take only the stems the generic path refuses
+    (out_channels % 16 != 0); "all" -> every 3 -> Cout 3x3 s2 p1 stem inside
+    their contract; "0" -> none, the routing from before them."""
+    return os.environ.get("AMDTRAIN_STEM3X3", "")
+
+
+def stem3x3_ok(cin: int, cout: int) -> bool:
+    """Host contract of stem3x3_fwd / stem3x3_wgrad.  Pure Python."""
+    return cin == 3 and cout % 8 == 0 and 8 <= cout <= 64
+
+
+class _Stem3x3(torch.autograd.Function):
+    """3 -> Cout 3x3 stride-2 pad-1 conv on the raw channels-last input
+    (stem3x3.hip): forward with the BN-statistics partials as a second,
+    non-differentiable output, weight gradient from the same halo tiles.
+    There is no input gradient: ``conv_stem3x3`` sends an input that needs
+    one to the generic path."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.bfloat16)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        e = require_ext()
+        n, _, h, w = x.shape
+        cout = weight.shape[0]
+        x4 = x.contiguous(memory_format=torch.channels_last) \
+            .permute(0, 2, 3, 1)                       # [N, H, W, 3]
+        y2d, stats = e.stem3x3_fwd(x4, weight, _fuse_stats_enabled())
+        ctx.save_for_backward(x4)
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        ctx.mark_non_differentiable(stats)
+        return y2d.view(n, ho, wo, cout).permute(0, 3, 1, 2), stats
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y: torch.Tensor, _grad_stats=None):
+        e = require_ext()
+        x4, = ctx.saved_tensors
+        assert not ctx.needs_input_grad[0]
+        dw = None
+        if ctx.needs_input_grad[1]:
+            gy2d = _rows(grad_y.contiguous(
+                memory_format=torch.channels_last)).to(torch.bfloat16)
+            dw = e.stem3x3_wgrad(gy2d, x4)             # [Cout, 27] f32
+            dw = dw.view(-1, 3, 3, 3).permute(0, 3, 1, 2) \
+                .contiguous(memory_format=torch.channels_last)
+        return None, dw
+
+
+def conv_stem3x3(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """3x3 stride-2 pad-1 conv of a 3-channel input inside ``stem3x3_ok``.
+    An input that needs a gradient takes the generic path for that call."""
+    if x.requires_grad and torch.is_grad_enabled():
+        return conv_stem_mfma(x, weight, 2, 1)
+    y, stats = _Stem3x3.apply(x, weight)
+    if stats.numel():
+        y._amdtrain_bn_stats = stats
+    return y
+
+
 def _conv1x1_env_default() -> str:
     return os.environ.get("AMDTRAIN_CONV1X1", "custom")
 
@@ -897,7 +958,10 @@ class AmdConv2d(nn.Conv2d):
     (``pw_wide_ok``), the pointwise GEMM on the 8 grid (pwgemm8.hip;
     AMDTRAIN_PWWIDE=0 likewise),
     3x3 pad-1 s1/s2 -> implicit GEMM
-    (conv3x3.hip), anything else without an input gradient (the 7x7
+    (conv3x3.hip), the 3 -> Cout 3x3 s2 p1 RGB stem with Cout % 8 == 0,
+    Cout <= 64 and no input gradient -> the direct kernels of stem3x3.hip
+    (by default only Cout % 16 != 0; AMDTRAIN_STEM3X3=all takes every such
+    stem, =0 none), anything else without an input gradient (the 7x7
     stem) -> generic element-gather implicit GEMM (conv_stem.hip).
     Depthwise 3x3 pad-1 s1/s2 (groups == in == out channels, C % 8 == 0)
     -> vectorised stencil (dwconv.hip); depthwise 5x5 pad-2 s1/s2 under the
@@ -988,6 +1052,17 @@ class AmdConv2d(nn.Conv2d):
                     and os.environ.get("AMDTRAIN_CONV3X3", "custom")
                     == "custom"):
                 return conv3x3_mfma(x, self.weight, self.stride[0])
+            # RGB stem: by default only the widths the generic path refuses
+            if (self.kernel_size == (3, 3) and self.stride == (2, 2)
+                    and self.padding == (1, 1)
+                    and stem3x3_ok(self.in_channels, self.out_channels)
+                    and not x.requires_grad
+                    and os.environ.get("AMDTRAIN_CONVSTEM", "custom")
+                    == "custom"):
+                mode = _stem3x3_mode()
+                if mode == "all" or (mode != "0"
+                                     and self.out_channels % 16 != 0):
+                    return conv_stem3x3(x, self.weight)
             if (self.out_channels % 16 == 0
                     and self.stride[0] == self.stride[1]
                     and self.padding[0] == self.padding[1]

@@ -105,6 +105,11 @@ std::vector<at::Tensor> pw_gemm(at::Tensor A, at::Tensor B, bool want_stats,
 std::vector<at::Tensor> pw8_gemm(at::Tensor A, at::Tensor B, bool want_stats,
                                  long n_tile);
 
+// stem3x3.hip (3 -> Cout 3x3 s2 p1 on the raw [N,H,W,3] input)
+std::vector<at::Tensor> stem3x3_fwd(at::Tensor x, at::Tensor w,
+                                    bool want_stats);
+at::Tensor stem3x3_wgrad(at::Tensor dy, at::Tensor x);
+
 // conv3x3.hip
 at::Tensor conv3x3_fwd(at::Tensor x2d, long Nn, long H, long W, long stride,
                        at::Tensor w2d, bool nt64, long epi);
@@ -260,6 +265,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("want_stats"), py::arg("max_blocks") = -1);
   m.def("pw8_gemm", &pw8_gemm, py::arg("A"), py::arg("B"),
         py::arg("want_stats"), py::arg("n_tile") = 0);
+  m.def("stem3x3_fwd", &stem3x3_fwd, py::arg("x"), py::arg("w"),
+        py::arg("want_stats"));
+  m.def("stem3x3_wgrad", &stem3x3_wgrad, py::arg("dy"), py::arg("x"));
   m.def("conv3x3_fwd", &conv3x3_fwd, py::arg("x2d"), py::arg("Nn"),
         py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("w2d"),
         py::arg("nt64") = true, py::arg("epi") = -1);

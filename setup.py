@@ -38,6 +38,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "pwconv.hip"),
         os.path.join(CSRC, "pwgemm8.hip"),
         os.path.join(CSRC, "se.hip"),
+        os.path.join(CSRC, "stem3x3.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
